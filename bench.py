@@ -10,16 +10,18 @@ m runs on GPU m % N (the reference's mapId % folderPrefixes sharding,
 S3ShuffleDispatcher.scala:142-143); per-GPU work is fixed -> weak scaling; the compress path
 has no exchange step, so there is no data-path collective (only the timing barrier).
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
          python bench.py --gpus N ...   (no launcher: re-executes itself under torch.distributed.run)
 Rank 0's LAST stdout line is the ONE compact JSON line of the contract (< 4 KB) with `roofline`
-(dominant kernel: the LZ4 block-compress kernel, HIP-event timed on the library's own stream) and
-`cpu_baseline` (the CPU oracle driving liblz4 1.9.3 on the host cores; checker code, timed here only
-as the baseline).  The plain N=1 command also runs the other BASELINE configurations: their full
-records go to bench_secondary.json and to an EARLIER stdout line, a short summary to the line
-before the headline.
+(dominant kernel: the LZ4 block-compress kernel, HIP-event timed on the library's own stream).
+A plain run only sets up, warms up, times the K steps, writes the outputs of the last step when
+--dump-outputs is given, and prints that line (`cpu_baseline` null).  --full adds the rest:
+`cpu_baseline` (the CPU oracle driving liblz4 1.9.3 on the host cores; checker code, timed here
+only as the baseline), the untimed comparison of the timed outputs with the oracle, and for the
+N=1 headline command the other BASELINE configurations, whose full records go to
+bench_secondary.json and to an EARLIER stdout line, a short summary to the line before the headline.
 """
 from __future__ import annotations
 
@@ -43,6 +45,9 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md)
 HBM_COPY_CEILING_GBPS = 6290.0  # measured float4-copy ceiling, same guide
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all arrays together
+DUMP_SAMPLE_BYTES = 4 << 20     # --dump-outputs: sampled output bytes in all (float32 each: 16 MiB)
+DUMP_SEED = 20251016            # --dump-outputs: sample positions of map task m are drawn from default_rng(DUMP_SEED + m)
 
 WORKLOADS = {
     # name: (generator, partitions, codec, checksum)
@@ -274,7 +279,7 @@ def parse_args():
                     help="skip the untimed image_verified check after a compress leg (profiling runs: it adds checksum launches)")
     ap.add_argument("--secondary", dest="secondary", action="store_true", default=None,
                     help="after the headline, run short (3-step) passes of the other BASELINE.json configurations and attach "
-                         "them as `secondary` to the JSON line (default: on for the plain N=1 headline command)")
+                         "them as `secondary` to the JSON line (implies --full; default: on for the N=1 headline command with --full)")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false")
     ap.add_argument("--host-path-only", action="store_true", help="run only the host-buffer leg (run_host_path) and print it")
     ap.add_argument("--hbm-stages-only", action="store_true", help="run only the HBM-bound stage lines (run_hbm_stages) and print them")
@@ -283,7 +288,21 @@ def parse_args():
                     help="no timing: every rank reports (rank, local rank, device, its map ids); rank 0 checks that "
                          "mapId %% nGPU covers every map task exactly once and prints the table as one JSON line "
                          "(backend nccl on GPUs, gloo without)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, the untimed checks of the timed "
+                         "outputs (image_verified against the oracle, bytes_verified against the source) and, for the N=1 headline command, the "
+                         "secondary configurations, block-size sweep, HBM-bound stages and host-buffer path (see --secondary); "
+                         "off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's map tasks) as DIR/<name>.npy "
+                         "in float32 / float64: index and checksums or decoded sizes, the CRC32 of every whole output and a "
+                         "fixed, seeded sample of its bytes (%d MiB at most in all)" % (DUMP_MAX_BYTES >> 20))
+    args = ap.parse_args()
+    if args.secondary:
+        args.full = True
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 _GEN_CACHE = {}  # (generator, partitions, map id, bytes) -> host arrays: the secondary passes reuse the headline's inputs
@@ -459,6 +478,58 @@ def verify_images(workload, codec_id, algo_id, codec, tasks, map_ids, n_bytes, l
     return True
 
 
+def dump_sample_positions(map_id: int, size: int, k: int) -> np.ndarray:
+    """the k byte positions of a map task's output that --dump-outputs keeps: drawn from default_rng(DUMP_SEED + map id),
+    scaled to the output's size, sorted"""
+    u = np.sort(np.random.default_rng(DUMP_SEED + int(map_id)).random(k))
+    return np.minimum((u * size).astype(np.int64), max(size - 1, 0))
+
+
+def dump_outputs(out_dir: str, tasks, map_ids, last_result, decompress: bool):
+    """What the last timed step handed its caller, for comparing two builds output for output (untimed, rank 0's map tasks).
+    Map side: per map task the index and per-partition checksums the call returned and the .data image it left in HBM;
+    reduce side: the decoded bytes.  The whole images / decoded outputs are represented by their size, their zlib CRC32 and a
+    sample of their bytes at dump_sample_positions.  Every array is float64, the byte sample float32: all values are exact.
+    The arrays stay within DUMP_MAX_BYTES: per-partition arrays above half of it keep a seeded subset of the partitions
+    (partition_ids), and the byte sample gets what is left, DUMP_SAMPLE_BYTES at most."""
+    import zlib
+
+    n = len(tasks)
+    name = "decoded" if decompress else "data_image"
+    sizes = [int(t["u"]) if decompress else int(last_result[i][0]) for i, t in enumerate(tasks)]
+    arrays = {"map_ids": np.asarray(map_ids, np.float64), name + "_bytes": np.asarray(sizes, np.float64)}
+    if not decompress:
+        index = np.stack([np.asarray(r[1], np.int64) for r in last_result])
+        sums = np.stack([np.asarray(r[2], np.int64) for r in last_result]) if all(r[2] is not None for r in last_result) else None
+        parts = index.shape[1] - 1
+        per_part = 8 * n * (1 if sums is None else 2)
+        if per_part * (parts + 1) > DUMP_MAX_BYTES // 2:
+            keep = max(1, (DUMP_MAX_BYTES // 2) // per_part)
+            sel = np.sort(np.random.default_rng(DUMP_SEED).choice(parts, size=keep, replace=False))
+            arrays["partition_ids"] = sel.astype(np.float64)
+        else:
+            sel = np.arange(parts + 1)
+        arrays["index"] = index[:, sel].astype(np.float64)
+        if sums is not None:
+            arrays["checksums"] = sums[:, sel[sel < parts]].astype(np.float64)
+    fixed = sum(a.nbytes for a in arrays.values()) + 8 * n  # (+ the CRC32s)
+    k = min([max(0, min(DUMP_SAMPLE_BYTES, (DUMP_MAX_BYTES - fixed) // 4) // n)] + sizes)
+    crcs, samples = [], []
+    for i, t in enumerate(tasks):
+        host = (t["out"] if decompress else t["dst"])[:sizes[i]].cpu().numpy()
+        crcs.append(zlib.crc32(host) & 0xFFFFFFFF)
+        samples.append(host[dump_sample_positions(map_ids[i], sizes[i], k)])
+    arrays[name + "_crc32"] = np.asarray(crcs, np.float64)
+    arrays[name + "_sample"] = np.stack(samples).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {n} map tasks need {total} bytes even without a byte sample (bound {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+    print(f"dump-outputs: {len(arrays)} arrays, {total} bytes -> {out_dir}", file=sys.stderr)
+
+
 def dry_run(args, rank: int, local_rank: int, world: int, launched: bool):
     """Validate rank <-> device <-> mapId without touching the codec (S3ShuffleDispatcher.scala:142-143 rule)."""
     import torch
@@ -497,9 +568,9 @@ def dry_run(args, rank: int, local_rank: int, world: int, launched: bool):
             raise SystemExit(2)
 
 
-def run_workload(args, rank: int, local_rank: int, world: int, dist):
+def run_workload(args, rank: int, local_rank: int, world: int, dist, dump_dir=None):
     """One measured workload: W warmup + K timed steps of the hot path over this rank's map tasks.  Returns the
-    result dict on rank 0 (None elsewhere)."""
+    result dict on rank 0 (None elsewhere).  dump_dir: write what the last timed step returned there (dump_outputs)."""
     import torch
     import s3shuffle
     from s3shuffle import sharding
@@ -702,11 +773,13 @@ def run_workload(args, rank: int, local_rank: int, world: int, dist):
     elapsed = time.perf_counter() - t0
     if gc_was_on:
         gc.enable()
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, tasks, map_ids, last_result, decompress)
 
     # reduce side: the timed calls check status and size only, and the per-partition checksum covers the COMPRESSED bytes —
     # so every decoded map output is compared with its source, byte for byte, once, after the timed region (untimed)
     bytes_verified = None
-    if decompress:
+    if decompress and args.full:
         bytes_verified = all(bool(torch.equal(t["out"], t["src"])) for t in tasks)
         if not bytes_verified:
             raise SystemExit(f"{args.workload}: decoded bytes differ from the source")
@@ -715,7 +788,7 @@ def run_workload(args, rank: int, local_rank: int, world: int, dist):
     # timed call left in HBM is hashed on the device (the library's own CRC32 over dst[:total]) and compared, together with the
     # index and the checksums, with the oracle's image of the same map output computed on the host
     image_verified = None
-    if not decompress and not args.no_image_check:
+    if not decompress and args.full and not args.no_image_check:
         image_verified = verify_images(args.workload, codec_id, algo_id, codecs[0], tasks, map_ids, n_bytes, last_result)
         if dist:  # every rank checks its own map outputs; the line reports the AND over ranks
             iv = torch.tensor([int(image_verified)], dtype=torch.int32, device=dev)
@@ -831,9 +904,9 @@ def run_workload(args, rank: int, local_rank: int, world: int, dist):
         }
         if image_verified is not None:
             out["image_verified"] = bool(image_verified)  # CRC32 of every task's .data image in HBM + index + checksums == the oracle's, after the timed region
-        if decompress:
+        if bytes_verified is not None:
             out["bytes_verified"] = bool(bytes_verified)  # torch.equal(decoded, source) for every map task of the step, after the timed region
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if codec_name == "zstd":
                 cb = cpu_baseline_zstd_decompress(args.workload, args.cpu_seconds, args.map_mib)
             elif codec_name == "lzf":
@@ -1298,8 +1371,8 @@ def self_launch(args) -> int:
 
 def main():
     args = parse_args()
-    if args.secondary is None:  # plain headline command only (the driver's); profiling / A-B commands stay short
-        args.secondary = (args.gpus == 1 and args.workload == "terasort-10g-200p-lz4" and args.direction == "compress"
+    if args.secondary is None:  # the headline command with --full only; profiling / A-B commands stay short
+        args.secondary = (args.full and args.gpus == 1 and args.workload == "terasort-10g-200p-lz4" and args.direction == "compress"
                           and not args.no_cpu_baseline and not args.dry_run and args.map_mib == 128)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1336,7 +1409,7 @@ def main():
     if args.hbm_stages_only:
         print(json.dumps({"hbm_bound_stages": run_hbm_stages(args, local_rank)}), flush=True)
         return
-    out = run_workload(args, rank, local_rank, world, dist)
+    out = run_workload(args, rank, local_rank, world, dist, dump_dir=args.dump_outputs)
     if rank == 0:
         # stdout: [full record incl. secondaries, one long line] [secondary summary, short] [THE headline, short, LAST]
         sec_file = None

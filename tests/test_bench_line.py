@@ -87,3 +87,78 @@ def test_plain_gpus_2_launches_its_own_ranks():
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["ok"] and d["world"] == 2 and d["backend"] == "gloo"
     assert [r["map_ids"] for r in sorted(d["ranks"], key=lambda r: r["rank"])] == [[0, 2, 4], [1, 3, 5]]
+
+
+def test_dump_outputs_are_exact_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: what the last timed step returned, as float32 / float64 arrays that hold every value exactly, under the
+    size bound, the byte sample at the seeded positions, the same for the same outputs (CPU tensors stand in for the device
+    buffers); map side and reduce side"""
+    import zlib
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    rng = np.random.default_rng(5)
+    tasks, last = [], []
+    for m in range(3):
+        total = 50_000 + 1000 * m
+        dst = torch.from_numpy(rng.integers(0, 256, total + 77, dtype=np.uint8))
+        index = np.concatenate([[0], np.sort(rng.integers(0, total, 6)), [total]]).astype(np.int64)
+        sums = rng.integers(0, 1 << 32, 7, dtype=np.int64)
+        tasks.append({"dst": dst, "out": dst[:40_000 + m], "u": 40_000 + m})
+        last.append((total, index, sums))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), tasks, [0, 2, 4], last, False)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["checksums", "data_image_bytes", "data_image_crc32", "data_image_sample", "index", "map_ids"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES
+    assert got["map_ids"].tolist() == [0, 2, 4] and got["data_image_bytes"].tolist() == [50_000, 51_000, 52_000]
+    k = min(bench.DUMP_SAMPLE_BYTES // 3, 50_000)
+    assert got["data_image_sample"].shape == (3, k)
+    for i, (total, index, sums) in enumerate(last):
+        img = tasks[i]["dst"][:total].numpy()
+        assert np.array_equal(got["index"][i], index) and np.array_equal(got["checksums"][i], sums)
+        assert got["data_image_crc32"][i] == zlib.crc32(img)
+        pos = np.sort(np.random.default_rng(bench.DUMP_SEED + 2 * i).random(k)) * total
+        assert np.array_equal(got["data_image_sample"][i], img[pos.astype(np.int64)].astype(np.float32))
+    assert not np.array_equal(got["data_image_sample"][0], np.sort(got["data_image_sample"][0]))  # (positions, not values, sorted)
+    for f in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+    # reduce side: the decoded bytes
+    bench.dump_outputs(str(tmp_path / "dec"), tasks, [1, 3, 5], last, True)
+    dec = {f.stem: np.load(f) for f in (tmp_path / "dec").iterdir()}
+    assert sorted(dec) == ["decoded_bytes", "decoded_crc32", "decoded_sample", "map_ids"]
+    for i in range(3):
+        out = tasks[i]["out"].numpy()
+        assert dec["decoded_bytes"][i] == out.size and dec["decoded_crc32"][i] == zlib.crc32(out)
+        assert np.array_equal(dec["decoded_sample"][i], out[bench.dump_sample_positions(2 * i + 1, out.size, 40_000)])
+
+
+def test_dump_outputs_keep_the_bound_with_many_partitions(tmp_path, monkeypatch):
+    """per-partition arrays larger than half the bound keep a seeded subset of the partitions; the byte sample shrinks to fit"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 16)
+    parts, n = 2000, 3
+    tasks, last = [], []
+    for m in range(n):
+        dst = torch.full((9000,), m, dtype=torch.uint8)
+        index = np.linspace(0, 9000, parts + 1).astype(np.int64)
+        tasks.append({"dst": dst})
+        last.append((9000, index, np.arange(parts, dtype=np.int64) * (m + 1)))
+    bench.dump_outputs(str(tmp_path), tasks, list(range(n)), last, False)
+    got = {f.stem: np.load(f) for f in tmp_path.iterdir()}
+    assert sum(a.nbytes for a in got.values()) <= 1 << 16
+    sel = got["partition_ids"].astype(np.int64)
+    assert 0 < sel.size < parts and (np.diff(sel) > 0).all() and got["index"].shape == got["checksums"].shape == (n, sel.size)
+    for m in range(n):
+        assert np.array_equal(got["checksums"][m], sel * (m + 1)) and np.array_equal(got["index"][m], last[m][1][sel])
+        assert (got["data_image_sample"][m] == m).all()
+    assert got["data_image_sample"].shape[1] > 0

@@ -1,37 +1,60 @@
-"""f1 as something checkable without a JDK: scala/patches/0001-gpu-codec.patch must apply to the
-reference's own writer / reader / dispatcher (`git apply --check` on a scratch copy of /root/reference — skipped on
-the GPU box, where the reference does not exist), and the names that cross between the patch and the shim sources
-under scala/ must exist on the other side (config keys, methods)."""
+"""f1 as something checkable without a JDK: scala/patches/0001-gpu-codec.patch must be a well-formed
+patch of the plugin's own writer / reader / dispatcher whose hunks leave the call sites, config keys and gates in place and
+keep every bracket of the code they replace balanced, and the names that cross between the patch and the shim sources
+under scala/ must exist on the other side (config keys, methods).  Everything is read from the patch and the shim: the
+plugin's sources are not part of this repository."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATCH = os.path.join(ROOT, "scala", "patches", "0001-gpu-codec.patch")
 SHIM = os.path.join(ROOT, "scala", "org", "apache", "spark", "shuffle", "gpu")
-REF = "/root/reference"
+BASE = "src/main/scala/org/apache/spark/"
+WRITER = BASE + "shuffle/S3ShuffleMapOutputWriter.scala"
+SPILL_WRITER = BASE + "shuffle/S3SingleSpillShuffleMapOutputWriter.scala"
+DISPATCHER = BASE + "shuffle/helper/S3ShuffleDispatcher.scala"
+READER = BASE + "storage/S3ShuffleReader.scala"
+_HUNK = re.compile(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@")
 
 
 def _read(*parts):
     return open(os.path.join(*parts), errors="ignore").read()
 
 
+def _parse_patch(text):
+    """path under b/ -> its hunks in order: old / new start and length as the header says, the lines the hunk expects in the
+    plugin's file (context + removed) and the lines it leaves there (context + added)"""
+    files, cur, hunk = {}, None, None
+    for line in text.splitlines():
+        if line.startswith("+++ b/"):
+            cur, hunk = files.setdefault(line[6:].strip(), []), None
+        elif line.startswith("--- "):
+            hunk = None
+        elif cur is not None and _HUNK.match(line):
+            m = _HUNK.match(line)
+            hunk = {"old_start": int(m.group(1)), "old_len": int(m.group(2) or 1), "new_start": int(m.group(3)),
+                    "new_len": int(m.group(4) or 1), "pre": [], "post": []}
+            cur.append(hunk)
+        elif hunk is not None and line[:1] in (" ", "-", "+", ""):
+            if line[:1] != "+":
+                hunk["pre"].append(line[1:])
+            if line[:1] != "-":
+                hunk["post"].append(line[1:])
+        elif hunk is not None and not line.startswith("\\"):  # ("\ No newline at end of file" is allowed)
+            raise AssertionError("not a patch line: %r" % line)
+    return files
+
+
 @pytest.fixture(scope="module")
-def patched_tree(tmp_path_factory):
-    if not os.path.isdir(os.path.join(REF, "src", "main", "scala")):
-        pytest.skip("reference sources not present (GPU box)")
-    top = tmp_path_factory.mktemp("ref")
-    shutil.copytree(os.path.join(REF, "src"), os.path.join(top, "src"))
-    chk = subprocess.run(["git", "apply", "--check", "--verbose", PATCH], cwd=top, capture_output=True, text=True)
-    assert chk.returncode == 0, chk.stderr
-    subprocess.run(["git", "apply", PATCH], cwd=top, check=True)
-    # the shim sources go next to the plugin's own packages
-    dst = os.path.join(top, "src", "main", "scala", "org", "apache", "spark", "shuffle", "gpu")
-    shutil.copytree(SHIM, dst)
-    return str(top)
+def hunks():
+    return _parse_patch(_read(PATCH))
+
+
+def _post(hunks, rel):
+    """what the patch writes into one of the plugin's files: the post-images of its hunks, in order"""
+    return "\n// (unchanged lines of the plugin)\n".join("\n".join(h["post"]) for h in hunks[rel])
 
 
 def test_patch_touches_the_four_call_sites():
@@ -42,10 +65,22 @@ def test_patch_touches_the_four_call_sites():
         "S3SingleSpillShuffleMapOutputWriter.scala"]
 
 
-def test_patch_applies_to_the_reference(patched_tree):
-    w = _read(patched_tree, "src/main/scala/org/apache/spark/shuffle/S3ShuffleMapOutputWriter.scala")
+def test_patch_is_well_formed_and_carries_the_call_sites(hunks):
+    """every hunk is as long as its header says, the hunks of a file are in order and do not overlap, and each one shifts the
+    following lines by exactly what it adds (what `git apply` relies on); the writer and the reader call the shim"""
+    assert sorted(hunks) == sorted((WRITER, SPILL_WRITER, DISPATCHER, READER))
+    for rel, hs in hunks.items():
+        assert hs, rel
+        shift, end = 0, 0
+        for h in hs:
+            assert len(h["pre"]) == h["old_len"] and len(h["post"]) == h["new_len"], (rel, h["old_start"])
+            assert h["old_start"] > end and h["new_start"] == h["old_start"] + shift, (rel, h["old_start"])
+            assert h["pre"] != h["post"], (rel, h["old_start"])
+            shift += h["new_len"] - h["old_len"]
+            end = h["old_start"] + h["old_len"] - 1
+    w = _post(hunks, WRITER)
     assert "gpu.append(reduceId, b, off, len)" in w and "return gpu.commit()" in w
-    r = _read(patched_tree, "src/main/scala/org/apache/spark/storage/S3ShuffleReader.scala")
+    r = _post(hunks, READER)
     assert "S3GpuBlockDecoder.decode(blockId, stream, jvmPlain)" in r
     # the reduce side on its own (round 4): JVM-written objects go through wrapStream inside the fallback stack, GPU-written
     # ones through the codec named by spark.shuffle.s3.gpu.codec; what reaches the deserializer is plain either way
@@ -53,14 +88,14 @@ def test_patch_applies_to_the_reference(patched_tree):
     assert "dispatcher.gpuReadEnabled && S3GpuBlockDecoder.accepts(blockId)" in r
 
 
-def test_config_keys_used_by_the_shim_are_defined_by_the_patch(patched_tree):
-    disp = _read(patched_tree, "src/main/scala/org/apache/spark/shuffle/helper/S3ShuffleDispatcher.scala")
+def test_config_keys_used_by_the_shim_are_defined_by_the_patch(hunks):
+    disp = _post(hunks, DISPATCHER)
     defined = set(re.findall(r"^\s*val (gpu\w+)\s*:", disp, re.M))
     used = set()
-    for d, _, names in os.walk(os.path.join(patched_tree, "src", "main", "scala")):
-        for n in names:
-            if n.endswith(".scala") and n != "S3ShuffleDispatcher.scala":
-                used |= set(re.findall(r"\b(?:dispatcher|d|S3ShuffleDispatcher\.get)\.(gpu\w+)", _read(d, n)))
+    # the plugin's own code uses no gpu* member: they appear in the patch's hunks and in the shim
+    for src in [_post(hunks, rel) for rel in hunks if rel != DISPATCHER] + \
+               [_read(SHIM, n) for n in sorted(os.listdir(SHIM)) if n.endswith(".scala")]:
+        used |= set(re.findall(r"\b(?:dispatcher|d|S3ShuffleDispatcher\.get)\.(gpu\w+)", src))
     assert used and used <= defined, (used - defined)
     # every key is documented where the maintainer looks for it
     integ = _read(ROOT, "INTEGRATION.md")
@@ -68,12 +103,12 @@ def test_config_keys_used_by_the_shim_are_defined_by_the_patch(patched_tree):
         assert key in integ, key
 
 
-def test_reduce_side_on_its_own_and_the_zstd_gate(patched_tree):
+def test_reduce_side_on_its_own_and_the_zstd_gate(hunks):
     """the Zstandard decoder and the big-block LZ4 decoder have a caller.  With JVM writers
     (spark.shuffle.compress=true) the patched reader still hands prefetched ranges to the library: lz4 of any block size,
     snappy up to 32k, zstd only for batch ranges of many small frames; never together with IO encryption or
     useSparkShuffleFetch.  The map side keeps its own gate (lz4 / snappy, blocks up to 32k)."""
-    disp = _read(patched_tree, "src/main/scala/org/apache/spark/shuffle/helper/S3ShuffleDispatcher.scala")
+    disp = _post(hunks, DISPATCHER)
     m = re.search(r"val gpuReadEnabled: Boolean = gpuEnabled \|\| \{(.*?)\n  \}", disp, re.S)
     assert m, "gpuReadEnabled"
     body = m.group(1)
@@ -162,20 +197,39 @@ def _brackets_balance(src):
     return "unclosed %r" % stack[-1:] if stack else None
 
 
-def test_scala_sources_are_structurally_sound(patched_tree):
-    """no scalac here: at least every bracket of the shim sources and of the four PATCHED reference files closes where it
-    should (comments and string literals lexed away) — an edit that drops a brace does not survive the CPU suite"""
+def _bracket_signature(src):
+    """the brackets of src that stay unmatched once every matched pair is gone: (closers in front, openers behind); a
+    mismatched pair is an error"""
+    stack, front, pairs = [], [], {")": "(", "]": "[", "}": "{"}
+    for ch in _strip_scala(src):
+        if ch in "([{":
+            stack.append(ch)
+        elif ch in pairs:
+            if stack:
+                assert stack[-1] == pairs[ch], "%r closes %r" % (ch, stack[-1])
+                stack.pop()
+            else:
+                front.append(ch)
+    return "".join(front), "".join(stack)
+
+
+def test_scala_sources_are_structurally_sound(hunks):
+    """no scalac here: at least every bracket of the shim sources closes where it should (comments and string literals
+    lexed away), and every hunk of the patch leaves the brackets it replaces in the plugin's four files open or closed as
+    they were — an edit that drops a brace does not survive the CPU suite"""
     files = [os.path.join(SHIM, f) for f in sorted(os.listdir(SHIM)) if f.endswith(".scala")]
     assert len(files) == 4
-    base = os.path.join(patched_tree, "src", "main", "scala", "org", "apache", "spark")
-    files += [os.path.join(base, "shuffle", "S3ShuffleMapOutputWriter.scala"),
-              os.path.join(base, "shuffle", "S3SingleSpillShuffleMapOutputWriter.scala"),
-              os.path.join(base, "shuffle", "helper", "S3ShuffleDispatcher.scala"),
-              os.path.join(base, "storage", "S3ShuffleReader.scala")]
     for f in files:
         assert _brackets_balance(_read(f)) is None, (f, _brackets_balance(_read(f)))
+    assert len(hunks) == 4
+    for rel, hs in hunks.items():
+        for h in hs:
+            pre, post = "\n".join(h["pre"]), "\n".join(h["post"])
+            assert _bracket_signature(pre) == _bracket_signature(post), (rel, h["new_start"], _bracket_signature(post))
     assert _brackets_balance("object A { def f(x: Int) = { x + 1 }") is not None  # (the check sees a dropped brace)
     assert _brackets_balance('object A { val s = "}" /* } */ }') is None
+    assert _bracket_signature("  }\n  def f = {\n    g(1)") == ("}", "{")
+    assert _bracket_signature("  }\n  def f = {\n    g(1)\n  }") != _bracket_signature("  }\n  def f = {\n    g(1)")
 
 
 def test_documented_keys_exist_where_the_document_says():
@@ -191,22 +245,6 @@ def test_documented_keys_exist_where_the_document_says():
             assert key in host and key not in patch, key
         else:
             assert '"%s"' % key in patch, key
-
-
-def test_reference_members_the_shim_uses_exist(patched_tree):
-    """the other direction: every S3ShuffleHelper.<member> and dispatcher.<member> the shim sources call is defined in the
-    (patched) reference — a renamed helper would otherwise only fail at scalac time, which nobody can run here"""
-    base = os.path.join(patched_tree, "src", "main", "scala", "org", "apache", "spark")
-    helper = _read(base, "shuffle", "helper", "S3ShuffleHelper.scala")
-    disp = _read(base, "shuffle", "helper", "S3ShuffleDispatcher.scala")
-    shim = "".join(_strip_scala(_read(SHIM, f)) for f in sorted(os.listdir(SHIM)) if f.endswith(".scala"))
-    used_helper = set(re.findall(r"S3ShuffleHelper\.(\w+)", shim))
-    used_disp = set(re.findall(r"\b(?:dispatcher|d|S3ShuffleDispatcher\.get)\.(\w+)", shim)) - {"get"}
-    assert used_helper and used_disp
-    for name in used_helper:
-        assert re.search(r"\bdef %s\b" % name, helper), name
-    for name in used_disp:
-        assert re.search(r"\b(?:val|def|lazy val)\s+%s\b" % name, disp), name
 
 
 def _call_args(src, start):

@@ -13,7 +13,7 @@ if [ -n "$2" ]; then
   bash tools/profile_sets.sh $tag "$2" 2>&1 | tail -60
   python tools/profile_report.py $tag ${3:-unknown} 2>&1 | tail -12
 fi
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_stdout.txt 2>$O/bench_full.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_stdout.txt 2>$O/bench_full.err
 tail -n 1 $O/bench_stdout.txt > $O/bench_headline.json      # THE line the driver parses (compact)
 tail -n 2 $O/bench_stdout.txt | head -n 1 > $O/bench_secondary_summary.json
 cp bench_secondary.json $O/bench_full.json                   # full record: headline with long descriptions + every secondary leg
