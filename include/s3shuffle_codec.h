@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define S3S_ABI_VERSION 8 /* 2: + segments entry points, page-locked staging, tuning options 6, 7;
+#define S3S_ABI_VERSION 9 /* 2: + segments entry points, page-locked staging, tuning options 6, 7;
                              3: + s3s_compress_map_outputs_batch_device;
                              4: + s3s_decompress_ranges_batch_device; decode variants {3, 4}, LZ4 parses {1, 9, 10};
                              5: + s3s_compress_map_outputs_batch / s3s_decompress_ranges_batch (host buffers),
@@ -74,7 +74,9 @@ extern "C" {
                              6: S3S_STATUS_NOT_RUN in the per-entry status of the batched calls (a call-level failure is told
                                 apart from an entry's own verdict);
                              7: + S3S_CODEC_LZF on the reduce side; LZ4Block frames above 32 KiB through the batch decoder;
-                             8: + S3S_CHECKSUM_CRC32C */
+                             8: + S3S_CHECKSUM_CRC32C;
+                             9: S3S_OPT_SNAPPY_BLOCK_SIZE up to 32 MiB (map side fragment-parallel), Snappy chunks of any
+                                decoded length up to 32 MiB through the batch decoder */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
@@ -110,8 +112,8 @@ enum {
                                     parse: S3S_E_UNSUPPORTED, the JVM codec writes them); the reduce side decodes frames
                                     of ANY block size whatever this option says */
   S3S_OPT_SNAPPY_BLOCK_SIZE = 2, /* spark.io.compression.snappy.blockSize, default 32768;
-                                    supported 1024..32768 (snappy-java raises smaller values
-                                    to 1024) */
+                                    supported 1..33554432 (snappy-java raises values below 1024
+                                    to 1024; larger values: S3S_E_UNSUPPORTED).  Since ABI 9 */
   S3S_OPT_PROFILE = 3,           /* 1: record per-stage HIP-event timings (s3s_stage_ms) */
   S3S_OPT_LZ4_VARIANT = 4,       /* tuning, identical output: 1 = general batch only (64 probes of the greedy
                                     parse per step), 10 (default) = lean exact 64-byte windows in front of

@@ -137,7 +137,25 @@ __device__ __forceinline__ void gather_item_body(
     }
     return;
   }
+  if (kind == kItemSnappyChunkHead) {
+    // a Snappy chunk above one fragment: i32 BE compressed length | varint32(len).  The fragments follow this item, so the
+    // raw block is the preamble plus what the scan placed between the first fragment's start and the last one's end.
+    if (tid < n) {
+      const int nfrag = (item.len + kSnappyFragment - 1) / kSnappyFragment;
+      const int vlen = n - 4;
+      const uint32_t clen = (uint32_t)(item_off[it + 1 + nfrag] - item_off[it + 1]) + (uint32_t)vlen;
+      uint32_t b;
+      if (tid < 4) b = clen >> (8 * (3 - tid));
+      else b = (((uint32_t)item.len >> (7 * (tid - 4))) & 0x7fu) | (tid - 4 + 1 < vlen ? 0x80u : 0u);
+      d[tid] = (uint8_t)b;
+    }
+    return;
+  }
   const uint8_t* slot = slots + (size_t)item.chunk * (size_t)slot_stride;
+  if (kind == kItemSnappyFrag) {  // a fragment's elements, behind the head item (and the fragments in front of it)
+    copy_bytes(d, slot + kSlotHeader, n, tid);
+    return;
+  }
   if (kind == kItemLz4Chunk) {
     if (sz & kRawFlag) {
       copy_bytes(d, slot + (kSlotHeader - kLz4FrameHeader), kLz4FrameHeader, tid);

@@ -141,9 +141,11 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
       ctx->lz4_block = value;
       return S3S_OK;
     case S3S_OPT_SNAPPY_BLOCK_SIZE:
+      // snappy-java takes any blockSize (values below 1 KiB are raised to 1 KiB, effective_block); chunks above one 64 KiB
+      // fragment are compressed fragment-parallel (ABI 9).  The cap is the batch decoder's largest block.
       if (value <= 0) return fail(ctx, S3S_E_INVALID, "snappy blockSize must be > 0");
-      if (value > kMaxBlock)
-        return fail(ctx, S3S_E_UNSUPPORTED, "snappy blockSize %lld > %d not supported", (long long)value, kMaxBlock);
+      if (value > kBatchMaxBlock)
+        return fail(ctx, S3S_E_UNSUPPORTED, "snappy blockSize %lld > %d not supported", (long long)value, kBatchMaxBlock);
       ctx->snappy_block = value;
       return S3S_OK;
     case S3S_OPT_PROFILE:
@@ -257,10 +259,12 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
   if (codec != S3S_CODEC_NONE) {
     for (int32_t g = 0; g < ns; g++) {
       const int64_t u = seg_offsets[g + 1] - seg_offsets[g];
-      if (u > 0) {
+      if (u > 0 && codec == S3S_CODEC_SNAPPY) {
+        snappy_segment_counts(bs, u, &n_items64, &n_chunks64);  // (chunks above 64 KiB: one item and slot per fragment)
+      } else if (u > 0) {
         const int64_t ch = (u + bs - 1) / bs;
         n_chunks64 += ch;
-        n_items64 += ch + 1;  // + LZ4 end frame / snappy stream header
+        n_items64 += ch + 1;  // + LZ4 end frame
       }
     }
   }
@@ -300,8 +304,11 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
         if (codec == S3S_CODEC_SNAPPY) h_items[it++] = Item{0, 0, kItemSnappyHeader, -1, p};
         for (int64_t pos = 0; pos < u; pos += bs) {
           const int32_t len = (int32_t)((u - pos) < bs ? (u - pos) : bs);
-          const int32_t kind = codec == S3S_CODEC_LZ4 ? (kItemLz4Chunk | (level << 8)) : kItemSnappyChunk;
-          h_items[it++] = Item{seg_offsets[g] + pos, len, kind, ch++, p};
+          if (codec == S3S_CODEC_SNAPPY) {
+            snappy_plan_chunk(h_items, it, ch, seg_offsets[g] + pos, len, p);
+            continue;
+          }
+          h_items[it++] = Item{seg_offsets[g] + pos, len, kItemLz4Chunk | (level << 8), ch++, p};
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
       }
@@ -333,10 +340,9 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
     if ((rc = ensure(ctx, B_ITEMS, items_bytes + 16))) return rc;
     if ((rc = ensure(ctx, B_PART_FIRST, pf_bytes))) return rc;
     // a slot holds one chunk's codec output: LZ4 payloads never exceed the chunk (RAW fallback), a raw
-    // snappy block can grow to MaxCompressedLength(chunk)
-    const int64_t slot_stride = codec == S3S_CODEC_SNAPPY
-                                    ? (int64_t)kSlotHeader + ((snappy_max_len(bs) + 15) & ~int64_t(15))
-                                    : (int64_t)kSlotHeader + ((bs + 15) & ~int64_t(15));
+    // snappy block can grow to MaxCompressedLength(chunk); a Snappy slot holds at most one 64 KiB fragment
+    const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs)
+                                                          : (int64_t)kSlotHeader + ((bs + 15) & ~int64_t(15));
     if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(n_chunks > 0 ? n_chunks : 1)))) return rc;
     if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
     if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * (size_t)(n_items + 1)))) return rc;
@@ -528,7 +534,9 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
     for (int32_t p = 0; p < k.num_partitions; p++) {
       const int64_t u = k.src_offsets[p + 1] - k.src_offsets[p];
       if (u < 0) return fail(ctx, S3S_E_INVALID, "task %d: offsets not monotonic at %d", t, p);
-      if (u > 0) {
+      if (u > 0 && codec == S3S_CODEC_SNAPPY) {
+        snappy_segment_counts(bs, u, &n_items64, &n_chunks64);
+      } else if (u > 0) {
         const int64_t ch = (u + bs - 1) / bs;
         n_chunks64 += ch;
         n_items64 += ch + 1;
@@ -579,8 +587,11 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
         if (codec == S3S_CODEC_SNAPPY) h_items[it++] = Item{0, 0, kItemSnappyHeader, -1, p};
         for (int64_t pos = 0; pos < u; pos += bs) {
           const int32_t len = (int32_t)((u - pos) < bs ? (u - pos) : bs);
-          const int32_t kind = codec == S3S_CODEC_LZ4 ? (kItemLz4Chunk | (level << 8)) : kItemSnappyChunk;
-          h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kind, ch++, p};
+          if (codec == S3S_CODEC_SNAPPY) {
+            snappy_plan_chunk(h_items, it, ch, delta + k.src_offsets[p] + pos, len, p);
+            continue;
+          }
+          h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kItemLz4Chunk | (level << 8), ch++, p};
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
       }
@@ -594,9 +605,8 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
     first_seg[(size_t)n_tasks] = seg;
   }
   const int32_t total_segs = first_seg[(size_t)n_tasks];
-  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY
-                                  ? (int64_t)kSlotHeader + ((snappy_max_len(bs) + 15) & ~int64_t(15))
-                                  : (int64_t)kSlotHeader + ((bs + 15) & ~int64_t(15));
+  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs)
+                                                        : (int64_t)kSlotHeader + ((bs + 15) & ~int64_t(15));
   if ((rc = ensure(ctx, B_ITEMS, items_bytes + 16))) return rc;
   if ((rc = ensure(ctx, B_PART_FIRST, 4 * np1))) return rc;
   if ((rc = ensure(ctx, B_SEG_START, 4 * np1))) return rc;

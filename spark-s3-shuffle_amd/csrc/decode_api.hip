@@ -293,7 +293,8 @@ int s3s_decompress_range_device(s3s_ctx* ctx, int codec, int checksum_algo, cons
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     finish_profile(3);
     const int32_t st = *reinterpret_cast<int32_t*>(&h_misc[1]);
-    if (st == S3S_E_UNSUPPORTED) return fail(ctx, S3S_E_UNSUPPORTED, "snappy block larger than %d bytes", kMaxBlock);
+    if (st == S3S_E_UNSUPPORTED)  // (the ring decoder, variant 3, keeps the 32 KiB limit; the batch decoder takes 32 MiB)
+      return fail(ctx, S3S_E_UNSUPPORTED, "snappy block larger than %d bytes", ctx->lz4_decode_variant == 3 ? kMaxBlock : kBatchMaxBlock);
     if (st != 0) return fail(ctx, S3S_E_BAD_FRAME, "Stream is corrupted");
     return S3S_OK;
   }

@@ -171,6 +171,10 @@ __device__ __forceinline__ int wave_scan_add(int v) {
 }
 
 enum { kFmtLz4 = 0, kFmtSnappy = 1, kFmtLzf = 2 };  // kFmtLzf (round 4): liblzf blocks of compress-lzf chunks, elements like Snappy's
+// the prefetch touch reads at most this much of a frame's stream (a 32 KiB block's worst case; the parse's own loads run
+// ahead of it from there on, for frames of every format and size)
+constexpr int kTouchBytes = kMaxBlock + kMaxBlock / 6 + 64;
+constexpr int kBigLitRecord = 896;  // Snappy chunks above 32 KiB: longest literal of a batch record (kernel, lit_cap)
 
 #ifdef S3S_LZ4_TIMING
 // phase accounting of the batch decoder (instrumented build only; tools/dec_timing.py): s_memtime ticks per phase
@@ -202,7 +206,7 @@ constexpr int kSnappyWalkTokens = S3S_SWALK_TOKENS;
 // in: d0 = the dword at the lane's stream position cpos.  out: isl (lanes whose element is a literal run), cx (byte-wise path),
 // r0 / r1 (the record halves of the generic front end), nxt (stream position of the element behind), islv (isl as 0 / 1).
 // Snappy: literal with its length in the tag (n6 + 1) or in one / two bytes behind it (n6 = 60 / 61; longer forms, a literal
-// past the block or above 32 KiB: byte-wise), copy with a 1-byte offset (length 4 + (n6 & 7), offset (tag >> 5) << 8 | next byte)
+// past the block or longer than lcap: byte-wise), copy with a 1-byte offset (length 4 + (n6 & 7), offset (tag >> 5) << 8 | next byte)
 // or a 2-byte offset (length n6 + 1); a 4-byte offset: byte-wise.
 // LZF: ctrl < 32: ctrl + 1 literals; else a back reference of (ctrl >> 5 [7: + next byte]) + 2 bytes, ((ctrl & 31) << 8 | last
 // byte) + 1 back.
@@ -223,7 +227,7 @@ constexpr int kSnappyWalkTokens = S3S_SWALK_TOKENS;
   "v_cndmask_b32_e64 %[hdr], %[hdr], 3, %[t1]\n\t" \
   "v_cmp_eq_u32_e64 %[isl], 0, %[ty]\n\t" \
   "v_add3_u32 %[nxt], %[cpos], %[hdr], %[len]\n\t" \
-  "v_cmp_lt_u32_e32 vcc, 0x8000, %[len]\n\t" \
+  "v_cmp_lt_u32_e32 vcc, %[lcap], %[len]\n\t" \
   "v_add_u32_e32 %[vt2], %[lane], %[hdr]\n\t" \
   "s_or_b64 %[cx], %[cx], vcc\n\t" \
   "v_cmp_lt_i32_e32 vcc, %[clen], %[nxt]\n\t" \
@@ -416,7 +420,7 @@ constexpr int kSnappyWalkTokens = S3S_SWALK_TOKENS;
                 [cpos] "=&v"(v_cpos), [d0] "=&v"(v_d0), [ty] "=&v"(v_ty), [n6] "=&v"(v_n6), [b1] "=&v"(v_b1), [w16] "=&v"(v_w16), \
                 [len] "=&v"(v_len), [hdr] "=&v"(v_hdr), [vt] "=&v"(v_t), [vt2] "=&v"(v_t2), [nxt] "=&v"(v_nxt), [nrel] "=&v"(v_nrel), \
                 [jmp] "=&v"(v_jmp), [m] "=&v"(v_m), [one] "=&v"(n_one), [c64] "=&v"(n_c64), [lma] "=&v"(n_lma) \
-              : [c] "s"(c), [clen] "s"(clen), [lane] "v"(lane), [rec] "s"(lds_addr(rec)), [mark] "s"(markb) \
+              : [c] "s"(c), [clen] "s"(clen), [lane] "v"(lane), [rec] "s"(lds_addr(rec)), [mark] "s"(markb), [lcap] "s"(lit_cap) \
               : "vcc", "scc", "memory");
 
 // kFmt selects the front end (token parse + byte-wise path); batches, rounds and the output window are the same:
@@ -440,11 +444,20 @@ __global__ __launch_bounds__(kWave, 8) void batch_decode_kernel(
   // are decoded here as well since round 4: the records of a batch keep stream offsets and output positions RELATIVE to
   // the batch's first token / first output byte (a batch of 64 fast-path sequences spans < 18 KiB of stream and < 35 KiB of
   // output), so nothing but the frame header's own 32-bit lengths depends on the block size.  kBatchMaxBlock = lz4-java's
-  // largest block (1 << 25).  Snappy chunks stay at 32 KiB (snappy-java's block size cannot exceed the fragment size here).
-  if (olen > (kFmt == kFmtSnappy ? kMaxBlock : kFmt == kFmtLzf ? 0xFFFF : kBatchMaxBlock) && (kFmt == kFmtSnappy || fr.method != 0x10)) {
+  // largest block (1 << 25).  Snappy chunks the same since ABI 9: snappy-java hands a whole spark.io.compression.snappy.blockSize
+  // chunk to snappy::RawCompress (which cuts it into 64 KiB fragments, but copies of other writers may reach anywhere back in
+  // the chunk: a copy outside the LDS history reads the destination, as LZ4's do).  A preamble above 1 << 25 (or above 2^31,
+  // negative here) is unsupported.
+  if ((kFmt == kFmtSnappy ? (uint32_t)olen > (uint32_t)kBatchMaxBlock : olen > (kFmt == kFmtLzf ? 0xFFFF : kBatchMaxBlock)) &&
+      (kFmt == kFmtSnappy || fr.method != 0x10)) {
     if (lane == 0) atomicExch(status, S3S_E_UNSUPPORTED);
     return;
   }
+  // Snappy / LZF: the longest literal element a batch record takes (longer ones go the byte-wise path).  A record keeps its
+  // stream offset and output position in 16 bits relative to the batch; a chunk of up to 32 KiB cannot overflow them, a
+  // larger one could with 64 long literals, so there 64 x (kBigLitRecord + 3 + 3) stream and 64 x (kBigLitRecord + 64)
+  // output bytes stay below 65 536.
+  const int lit_cap = olen <= kMaxBlock ? kMaxBlock : kBigLitRecord;
   if (olen == 0 && (kFmt == kFmtLz4 || clen == 0)) return;  // (end-of-stream frame; a frame the batched call skips)
   const uint8_t* c = comp + fr.comp_off;
   uint8_t* out = dst + frame_out[f];
@@ -455,7 +468,7 @@ __global__ __launch_bounds__(kWave, 8) void batch_decode_kernel(
   // dependent loads, one new cache line every other window, and a line that comes from HBM instead of L2 is on the chain.
   {
     uint32_t acc = 0;
-    const int lim = clen < kMaxBlock + kMaxBlock / 6 + 64 ? clen : kMaxBlock + kMaxBlock / 6 + 64;
+    const int lim = clen < kTouchBytes ? clen : kTouchBytes;
     for (int i = lane * 16; i + 16 <= lim; i += kWave * 16) {
       uint4 x;
       __builtin_memcpy(&x, c + i, 16);
@@ -479,7 +492,7 @@ __global__ __launch_bounds__(kWave, 8) void batch_decode_kernel(
     if (!bad && (int)ulen != olen) bad = true;
   }
   if (bad) {
-  } else if ((kFmt == kFmtSnappy ? clen > kMaxBlock + kMaxBlock / 6 + 64
+  } else if ((kFmt == kFmtSnappy ? (int64_t)clen > 32 + (int64_t)olen + olen / 6 + 64  // snappy MaxCompressedLength + slack
                                  : (int64_t)clen > (int64_t)olen + olen / (kFmt == kFmtLzf ? 16 : 255) + 16) &&
              !(kFmt != kFmtSnappy && fr.method == 0x10)) {
     bad = true;  // no block of that decoded size is that long (LZ4: LZ4_compressBound; a compressed frame is shorter than its block anyway)
@@ -1182,7 +1195,7 @@ __global__ __launch_bounds__(kWave, 8) void batch_decode_kernel(
                 hdr = 3;
               }
               nxt = cpos + hdr + len;
-              cx = n6 > 61u || nxt > clen || len > kMaxBlock;
+              cx = n6 > 61u || nxt > clen || len > lit_cap;
               is_lit = true;
               r0 = (uint32_t)len;
               r1 = (uint32_t)(lane + hdr) << 16;  // (window-relative; the batch's base is added when the record is stored)

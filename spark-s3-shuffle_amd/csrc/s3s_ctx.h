@@ -156,6 +156,37 @@ inline int lz4_level(int64_t block_size) {
 
 inline int64_t snappy_max_len(int64_t n) { return 32 + n + n / 6; }
 
+// ---- Snappy chunks and their plan records --------------------------------------------------------------------------
+// A chunk of up to one 64 KiB fragment is ONE kItemSnappyChunk item (one wavefront, one slot).  A larger chunk is a
+// kItemSnappyChunkHead item followed by one kItemSnappyFrag item per fragment: every fragment gets its own wavefront and
+// slot, so a 1 MiB block is 16 independent parses instead of a chain of 16 on one wavefront.
+inline int64_t snappy_chunk_items(int64_t len) { return len <= kSnappyFragment ? 1 : 1 + (len + kSnappyFragment - 1) / kSnappyFragment; }
+inline int64_t snappy_chunk_slots(int64_t len) { return len <= kSnappyFragment ? 1 : (len + kSnappyFragment - 1) / kSnappyFragment; }
+// items / slots of a segment of u bytes cut into chunks of bs (stream header item included)
+inline void snappy_segment_counts(int64_t bs, int64_t u, int64_t* items, int64_t* slots) {
+  const int64_t full = u / bs, rem = u % bs;
+  *items += 1 + full * snappy_chunk_items(bs) + (rem ? snappy_chunk_items(rem) : 0);
+  *slots += full * snappy_chunk_slots(bs) + (rem ? snappy_chunk_slots(rem) : 0);
+}
+// the items of one chunk [src_off, src_off + len) of partition `part`; `slot` counts the slots handed out
+template <typename ItemT>
+inline void snappy_plan_chunk(ItemT* items, int32_t& it, int32_t& slot, int64_t src_off, int32_t len, int32_t part) {
+  if (len <= kSnappyFragment) {
+    items[it++] = ItemT{src_off, len, kItemSnappyChunk, slot++, part};
+    return;
+  }
+  items[it++] = ItemT{src_off, len, kItemSnappyChunkHead, -1, part};
+  for (int32_t f = 0; f < len; f += kSnappyFragment) {
+    const int32_t fl = len - f < kSnappyFragment ? len - f : kSnappyFragment;
+    items[it++] = ItemT{src_off + f, fl, kItemSnappyFrag, slot++, part};
+  }
+}
+// bytes between the slots of one Snappy call: a slot holds at most one fragment's output
+inline int64_t snappy_slot_stride(int64_t bs) {
+  const int64_t n = bs < kSnappyFragment ? bs : kSnappyFragment;
+  return (int64_t)kSlotHeader + ((snappy_max_len(n) + 15) & ~int64_t(15));
+}
+
 inline int64_t effective_block(const s3s_ctx* ctx, int codec) {
   if (codec == S3S_CODEC_LZ4) return ctx ? ctx->lz4_block : 32768;
   if (codec == S3S_CODEC_SNAPPY) {

@@ -22,7 +22,9 @@ constexpr int kLz4MaxBlock = 65536;       // largest LZ4 chunk of the map side (
                                           // with the SAME 8192 x u16 table (byU16) - positions just need all 16 bits - so the
                                           // window engine takes them as it is; from 64 KiB + 11 on liblz4 switches to its
                                           // 4096 x u32 table with a 5-byte hash: another parse, not built
-constexpr int kBatchMaxBlock = 1 << 25;   // largest LZ4Block frame the batch decoder takes (lz4-java's MAX_BLOCK_SIZE)
+constexpr int kBatchMaxBlock = 1 << 25;   // largest LZ4Block frame the batch decoder takes (lz4-java's MAX_BLOCK_SIZE); also the
+                                          // largest Snappy chunk of both sides (spark.io.compression.snappy.blockSize, ABI 9)
+constexpr int kSnappyFragment = 65536;    // snappy::RawCompress compresses its input in independent 64 KiB fragments
 constexpr int kSlotHeader = 32;           // bytes reserved in front of a slot's payload
 constexpr int kLz4FrameHeader = 21;       // "LZ4Block" + token + 3 x i32
 constexpr int kSnappyStreamHeader = 16;
@@ -33,8 +35,17 @@ enum : int32_t {
   kItemLz4Chunk = 0,     // LZ4Block data frame (header + payload, payload may be RAW)
   kItemLz4End = 1,       // 21-byte end-of-stream frame
   kItemSnappyHeader = 2, // 16-byte SnappyOutputStream header
-  kItemSnappyChunk = 3   // i32 BE length + raw snappy
+  kItemSnappyChunk = 3,  // i32 BE length + raw snappy (a chunk of at most one fragment: <= kSnappyFragment bytes)
+  // a Snappy chunk above one fragment (ABI 9): a head item, then one kItemSnappyFrag item per 64 KiB fragment, in order
+  kItemSnappyChunkHead = 4,  // i32 BE length + varint32(len); len = the whole chunk.  Its size is known from len; the
+                             // length VALUE is the sum of the fragments' sizes, written by the gather (assemble.hip)
+  kItemSnappyFrag = 5        // one fragment's raw snappy elements (no preamble), compressed on its own wavefront
 };
+
+// bytes of snappy's varint32 preamble of a block of n bytes
+__host__ __device__ constexpr int snappy_varint_len(int64_t n) {
+  return n < (1 << 7) ? 1 : n < (1 << 14) ? 2 : n < (1 << 21) ? 3 : n < (1 << 28) ? 4 : 5;
+}
 
 struct Item {
   int64_t src_off;  // offset of the chunk in the uncompressed source (chunks only)

@@ -1,4 +1,4 @@
-// snappy_compress.hip — raw Snappy compression of 32 KiB shuffle chunks on CDNA4, byte-exact
+// snappy_compress.hip — raw Snappy compression of shuffle chunks on CDNA4, byte-exact
 // with the fragment compressor of Google snappy 1.1.8 (what oracle/s3s_oracle_snappy.c restates
 // and pins against libsnappy 1.1.8; the JVM's snappy-java 1.1.10.x bundles snappy 1.1.10 whose
 // heuristics differ — "parity unpinned" vs the JVM).
@@ -7,7 +7,11 @@
 // snappy::RawCompress) that produces the bytes arriving at S3ShuffleMapOutputWriter.scala:182-188
 // when spark.io.compression.codec=snappy.
 //
-// Same wave64 scheme as lz4_compress.hip: one wavefront per chunk, the sequential probe loop is
+// Chunks above one 64 KiB fragment (spark.io.compression.snappy.blockSize above 64k, ABI 9) are compressed the way
+// snappy::RawCompress does it, fragment by fragment with a fresh table each, but every fragment on its own wavefront
+// (kItemSnappyFrag items, s3s_ctx.h: snappy_plan_chunk); the chunk's i32 length and varint are written by the gather.
+//
+// Same wave64 scheme as lz4_compress.hip: one wavefront per fragment, the sequential probe loop is
 // evaluated 64 probes at a time with one speculative table insert + read-back, the clean prefix
 // decides which lanes saw the true candidate, the first matching lane wins, later lanes roll
 // back.  What differs from LZ4:
@@ -187,15 +191,16 @@ __device__ __forceinline__ int sn_first_diff16(uint4 x) {
   return r;
 }
 
-// The parse of one fragment (chunk <= 32 KiB).  Returns the number of bytes written.
-// kWin: exact windows in front of the general batch (header comment).
+// The parse of one fragment (len <= 64 KiB: positions, offsets and the table's u16 entries all fit 16 bits).  Returns the
+// number of bytes written.  kWin: exact windows in front of the general batch (header comment).  preamble: write the
+// varint32 of len first (a chunk of one fragment); a fragment of a larger chunk has none (the chunk's head item carries it).
 template <bool kWin>
-__device__ int snappy_compress_wave(const uint8_t* in, lds_u16* table, int len, uint8_t* out, int lane) {
+__device__ int snappy_compress_wave(const uint8_t* in, lds_u16* table, int len, uint8_t* out, int lane, bool preamble) {
   volatile lds_u16* T = table;
   int op = 0;
   // varint32 preamble: uncompressed length
   {
-    const int nb = len < 128 ? 1 : (len < 16384 ? 2 : 3);
+    const int nb = !preamble ? 0 : (len < 128 ? 1 : (len < 16384 ? 2 : 3));
     if (lane < nb) out[lane] = (uint8_t)(((uint32_t)len >> (7 * lane)) & 0x7f) | (lane + 1 < nb ? 0x80 : 0);
     op = nb;
   }
@@ -573,8 +578,9 @@ __global__ __launch_bounds__(kWave) void snappy_compress_kernel(
   const Item item = items[it];
   const int kind = item.kind & 0xff;
   const int lane = threadIdx.x;
-  if (kind != kItemSnappyChunk) {
+  if (kind != kItemSnappyChunk && kind != kItemSnappyFrag) {
     if (lane == 0 && kind == kItemSnappyHeader) item_size[it] = kSnappyStreamHeader;
+    if (lane == 0 && kind == kItemSnappyChunkHead) item_size[it] = 4u + (uint32_t)snappy_varint_len(item.len);
     return;
   }
   {
@@ -595,7 +601,12 @@ __global__ __launch_bounds__(kWave) void snappy_compress_kernel(
     if (acc == 0x12345678u && item.len < 0) table[0] = 1;  // (never taken: keeps the loads)
   }
   uint8_t* slot = slots + (size_t)item.chunk * (size_t)slot_stride;
-  const int clen = snappy_compress_wave<kWin>(src + item.src_off, (lds_u16*)table, item.len, slot + kSlotHeader, lane);
+  const bool whole = kind == kItemSnappyChunk;
+  const int clen = snappy_compress_wave<kWin>(src + item.src_off, (lds_u16*)table, item.len, slot + kSlotHeader, lane, whole);
+  if (!whole) {  // a fragment: its elements only (the head item's gather writes the chunk's length and preamble)
+    if (lane == 0) item_size[it] = (uint32_t)clen;
+    return;
+  }
   // SnappyOutputStream.dumpOutput(): i32 BE compressed length in front of the raw block
   if (lane < 4) slot[kSlotHeader - 4 + lane] = (uint8_t)((uint32_t)clen >> (8 * (3 - lane)));
   if (lane == 0) item_size[it] = 4u + (uint32_t)clen;

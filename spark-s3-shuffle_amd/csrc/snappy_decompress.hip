@@ -141,6 +141,8 @@ __global__ __launch_bounds__(kWave) void snappy_decompress_valu_kernel(
   const int olen = fr.orig_len, clen = fr.comp_len;
   const int lane = threadIdx.x;
   if (olen == 0 && clen == 0) return;  // a frame the batched call skips
+  // this decoder keeps Snappy chunks of at most 32 KiB (its ring and 16-bit offsets); larger ones, up to 32 MiB, are the
+  // batch decoder's (variant 4, the default: lz4_decode_batch.hip)
   if (olen > kMaxBlock) {
     if (lane == 0) atomicExch(status, S3S_E_UNSUPPORTED);
     return;
