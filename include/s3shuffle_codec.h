@@ -66,7 +66,7 @@
 extern "C" {
 #endif
 
-#define S3S_ABI_VERSION 9 /* 2: + segments entry points, page-locked staging, tuning options 6, 7;
+#define S3S_ABI_VERSION 10 /* 2: + segments entry points, page-locked staging, tuning options 6, 7;
                              3: + s3s_compress_map_outputs_batch_device;
                              4: + s3s_decompress_ranges_batch_device; decode variants {3, 4}, LZ4 parses {1, 9, 10};
                              5: + s3s_compress_map_outputs_batch / s3s_decompress_ranges_batch (host buffers),
@@ -76,7 +76,9 @@ extern "C" {
                              7: + S3S_CODEC_LZF on the reduce side; LZ4Block frames above 32 KiB through the batch decoder;
                              8: + S3S_CHECKSUM_CRC32C;
                              9: S3S_OPT_SNAPPY_BLOCK_SIZE up to 32 MiB (map side fragment-parallel), Snappy chunks of any
-                                decoded length up to 32 MiB through the batch decoder */
+                                decoded length up to 32 MiB through the batch decoder;
+                             10: + S3S_OPT_LZ4_BLOCK_SIZE_LARGE: LZ4 blocks up to 32 MiB on the map side (chunks of 65 547 bytes
+                                 or more through liblz4's 32-bit-table parse) */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
@@ -108,9 +110,10 @@ enum {
 /* option keys for s3s_set_option / s3s_get_option */
 enum {
   S3S_OPT_LZ4_BLOCK_SIZE = 1,    /* spark.io.compression.lz4.blockSize, default 32768;
-                                    map side: 64..65536 (liblz4's 16-bit-table parse; larger blocks are its 32-bit-table
-                                    parse: S3S_E_UNSUPPORTED, the JVM codec writes them); the reduce side decodes frames
-                                    of ANY block size whatever this option says */
+                                    map side: 64..65536 through THIS key (larger values: S3S_E_UNSUPPORTED, as before
+                                    ABI 10 - callers use that answer to keep the JVM codec; larger blocks are the caller's
+                                    explicit choice, key 8); the reduce side decodes frames of ANY block size whatever
+                                    this option says.  s3s_get_option returns the block size in force, whichever key set it */
   S3S_OPT_SNAPPY_BLOCK_SIZE = 2, /* spark.io.compression.snappy.blockSize, default 32768;
                                     supported 1..33554432 (snappy-java raises values below 1024
                                     to 1024; larger values: S3S_E_UNSUPPORTED).  Since ABI 9 */
@@ -124,9 +127,22 @@ enum {
   S3S_OPT_LZ4_VARIANT_USED = 7,  /* read-only: the parse (1 or 10) the last LZ4 compress call ran */
   S3S_OPT_SNAPPY_VARIANT = 6,    /* tuning, identical output: 0 = general batch only, 1 (default) = exact
                                     64-byte windows in front of it (several copies per round trip) */
-  S3S_OPT_LZ4_DECODE_VARIANT = 5 /* tuning, identical output, LZ4 and Snappy: 4 (default) = batch decoder
+  S3S_OPT_LZ4_DECODE_VARIANT = 5, /* tuning, identical output, LZ4 and Snappy: 4 (default) = batch decoder
                                     (one sequence per lane, dependency rounds, sliding LDS output window),
                                     3 = ring decoder (one sequence per step, parse on the vector ALU) */
+  S3S_OPT_LZ4_BLOCK_SIZE_LARGE = 8 /* since ABI 10: the same setting as key 1 with the range 64..33554432 (lz4-java's
+                                    MAX_BLOCK_SIZE; above: S3S_E_UNSUPPORTED, below 64: S3S_E_INVALID).  Chunks of 65 547
+                                    bytes or more are parsed as liblz4 parses them (4096 x u32 table, 5-byte hash, distance
+                                    test) by the general batch whatever S3S_OPT_LZ4_VARIANT says (the exact windows are
+                                    16-bit-table only; S3S_OPT_LZ4_VARIANT_USED reports the parse of the shorter chunks);
+                                    shorter chunks - a partition's tail - keep the 16-bit-table kernel.  One wavefront
+                                    parses one block, so a call needs ~2 560 blocks to fill the chip: throughput falls
+                                    with the block size, and without the exact windows match-dense data is no faster than
+                                    16 host cores already at 128k - measured only sort-like data at 128k gains (DESIGN.md 6d,
+                                    INTEGRATION.md 1a).  Workspace: every chunk - a partition's short tail included -
+                                    reserves a slot of 32 + blockSize bytes for the duration of the call, so a task of P
+                                    non-empty partitions holds at least P x blockSize (200 partitions at 32m: 6.4 GiB per
+                                    context); a call whose workspace cannot be allocated answers S3S_E_NOMEM */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */

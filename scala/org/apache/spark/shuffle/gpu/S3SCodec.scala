@@ -29,7 +29,8 @@ object S3SCodec {
   val OK = 0; val E_INVALID = -1; val E_CAPACITY = -2; val E_BAD_FRAME = -3; val E_CHECKSUM = -4; val E_HIP = -5
   val STATUS_NOT_RUN = -100 // per-entry status of a batch call that failed before this entry had a verdict: the call's return code is its error
   val OPT_LZ4_BLOCK_SIZE = 1; val OPT_SNAPPY_BLOCK_SIZE = 2
-  val ABI_VERSION = 9
+  val OPT_LZ4_BLOCK_SIZE_LARGE = 8 // ABI 10: key 1's setting with the range 64 .. 32m (key 1 keeps refusing values above 64k)
+  val ABI_VERSION = 10
 
   // ---- native entry points (jni/s3s_jni.c, one line each) -------------------------------------------------------
   @native def abiVersion(): Int

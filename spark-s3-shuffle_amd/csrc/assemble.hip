@@ -156,7 +156,7 @@ __device__ __forceinline__ void gather_item_body(
     copy_bytes(d, slot + kSlotHeader, n, tid);
     return;
   }
-  if (kind == kItemLz4Chunk) {
+  if (kind == kItemLz4Chunk || kind == kItemLz4ChunkU32) {
     if (sz & kRawFlag) {
       copy_bytes(d, slot + (kSlotHeader - kLz4FrameHeader), kLz4FrameHeader, tid);
       copy_bytes(d + kLz4FrameHeader, src + item.src_off, n - kLz4FrameHeader, tid);

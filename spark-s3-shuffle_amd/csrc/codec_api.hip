@@ -140,6 +140,14 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
         return fail(ctx, S3S_E_UNSUPPORTED, "lz4 blockSize %lld > %d not supported", (long long)value, kLz4MaxBlock);
       ctx->lz4_block = value;
       return S3S_OK;
+    case S3S_OPT_LZ4_BLOCK_SIZE_LARGE:
+      // the same setting with LZ4BlockOutputStream's whole range (ABI 10): chunks of kLz4U32From bytes or more are parsed by
+      // the byU32 kernel.  A key of its own: key 1's refusal above 64 KiB is what older callers rely on to keep the JVM codec
+      if (value < 64) return fail(ctx, S3S_E_INVALID, "lz4 blockSize must be >= 64, got %lld", (long long)value);
+      if (value > kBatchMaxBlock)
+        return fail(ctx, S3S_E_UNSUPPORTED, "lz4 blockSize %lld > %d not supported", (long long)value, kBatchMaxBlock);
+      ctx->lz4_block = value;
+      return S3S_OK;
     case S3S_OPT_SNAPPY_BLOCK_SIZE:
       // snappy-java takes any blockSize (values below 1 KiB are raised to 1 KiB, effective_block); chunks above one 64 KiB
       // fragment are compressed fragment-parallel (ABI 9).  The cap is the batch decoder's largest block.
@@ -172,7 +180,8 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
 int64_t s3s_get_option(const s3s_ctx* ctx, int key) {
   if (!ctx) return S3S_E_INVALID;
   switch (key) {
-    case S3S_OPT_LZ4_BLOCK_SIZE: return ctx->lz4_block;
+    case S3S_OPT_LZ4_BLOCK_SIZE:
+    case S3S_OPT_LZ4_BLOCK_SIZE_LARGE: return ctx->lz4_block;
     case S3S_OPT_SNAPPY_BLOCK_SIZE: return ctx->snappy_block;
     case S3S_OPT_PROFILE: return ctx->profile;
     case S3S_OPT_LZ4_VARIANT: return ctx->lz4_variant;
@@ -308,7 +317,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
             snappy_plan_chunk(h_items, it, ch, seg_offsets[g] + pos, len, p);
             continue;
           }
-          h_items[it++] = Item{seg_offsets[g] + pos, len, kItemLz4Chunk | (level << 8), ch++, p};
+          h_items[it++] = Item{seg_offsets[g] + pos, len, lz4_chunk_kind(len) | (level << 8), ch++, p};
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
       }
@@ -378,7 +387,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
         launch_lz4_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint32_t>(ctx, B_ITEM_CHECK) + i0,
                             dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE) + i0, dev<uint32_t>(ctx, B_WORK),
                             lz4_resident_waves(ctx), lz4_variant_run, ctx->stream,
-                            ctx->profile && i1 == n_items ? ctx->ev_hash : nullptr);
+                            ctx->profile && i1 == n_items ? ctx->ev_hash : nullptr, bs >= kLz4U32From);
       else
         launch_snappy_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
                                dev<uint32_t>(ctx, B_ITEM_SIZE) + i0, ctx->snappy_variant, ctx->stream);
@@ -591,7 +600,7 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
             snappy_plan_chunk(h_items, it, ch, delta + k.src_offsets[p] + pos, len, p);
             continue;
           }
-          h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kItemLz4Chunk | (level << 8), ch++, p};
+          h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, lz4_chunk_kind(len) | (level << 8), ch++, p};
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
       }
@@ -652,7 +661,7 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
     launch_lz4_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint32_t>(ctx, B_ITEM_CHECK),
                         dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<uint32_t>(ctx, B_WORK), lz4_resident_waves(ctx),
                         variant, ctx->stream,
-                        ctx->profile ? ctx->ev_hash : nullptr);
+                        ctx->profile ? ctx->ev_hash : nullptr, bs >= kLz4U32From);
   } else {
     launch_snappy_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
                            dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->snappy_variant, ctx->stream);

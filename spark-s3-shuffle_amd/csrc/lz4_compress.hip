@@ -19,6 +19,10 @@
 //       same-address LDS store is irrelevant.
 //   lean exact windows (kWindows = true, variant 10, default)  in front of the general batch: aligned 64-byte
 //       windows resolved with scalar mask arithmetic (see below; tests/model/lz4_window_model.cpp).
+// Chunks of 65 547 bytes and more (S3S_OPT_LZ4_BLOCK_SIZE_LARGE, ABI 10) are another parse in liblz4 - byU32: 4096 x u32 table,
+// a 12-bit hash of FIVE bytes, candidates more than 65 535 bytes back passed over - and another instantiation here
+// (TabLdsU32, lz4_compress_u32_kernel: the general batch only; tests/model/lz4_wave_model_u32.cpp).  The host plan routes a
+// chunk by its length (kItemLz4ChunkU32), so the kernels of the chunks below that stay what they were, instruction for instruction.
 // Earlier experiments (chunk staged in LDS, pipelined windows, run loop on the vector ALU, fused frame hash,
 // occupancy probes: variants 0, 2-7 of round 1) are in the git history and DESIGN.md §6, not in the product.
 // The frame's xxHash32 is computed by a separate streaming kernel.  Output: token / literal / offset bytes go
@@ -42,6 +46,17 @@ namespace {
 constexpr int kMfLimit = 12, kLastLiterals = 5, kMinMatch = 4;
 
 __device__ __forceinline__ uint32_t hash13(uint32_t v) { return (v * 2654435761u) >> 19; }
+
+// liblz4's hash of inputs of 65 547 bytes and more (LZ4_hash5, byU32, little-endian 64-bit host):
+//   ((read64(p) << 24) * 889523592379) >> 52  =  bits 28..39 of x * 889523592379,  x = the FIVE bytes at p.
+// v = bytes 0..3, b4 = a dword whose low byte is byte 4 (its other bits do not reach bits below 40 of the product).
+// 889523592379 = 0xCF'1BBCDCBB: bits 0..31 of the product come from v * lo, bits 32..39 from mulhi(v, lo) + v * 0xCF + b4 * lo.
+__device__ __forceinline__ uint32_t hash5_12(uint32_t v, uint32_t b4) {
+  constexpr uint32_t kLo = 0x1BBCDCBBu, kHi = 0xCFu;
+  const uint32_t p_lo = v * kLo;
+  const uint32_t p_hi = __umulhi(v, kLo) + v * kHi + b4 * kLo;
+  return ((p_lo >> 28) | (p_hi << 4)) & 0xfffu;
+}
 
 // Cumulative LZ4 skip schedule.  Probe index t (t = 0 is the "test next position" probe right
 // after a match, t >= 1 the search loop with searchMatchNb starting at 64) sits S(t) bytes
@@ -208,6 +223,8 @@ typedef __attribute__((address_space(3))) uint16_t lds_u16;
 
 struct TabLds {
   static constexpr bool kLds = true;
+  static constexpr bool kU32 = false;  // byU16: 8192 x u16, hash13 of four bytes, every candidate is within 65 535 bytes
+  typedef uint16_t pos_t;
   volatile lds_u16* t;
   struct Cell {
     volatile lds_u16* p;
@@ -216,6 +233,30 @@ struct TabLds {
   };
   __device__ __forceinline__ Cell operator[](uint32_t i) const { return Cell{t + i}; }
 };
+
+// byU32 (chunks of kLz4U32From bytes and more): 4096 x u32 - again 16 KiB of LDS -, hash5_12 of FIVE bytes, and a candidate
+// further back than 65 535 bytes is passed over without a compare.  General batch only (kWindows = false).
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+
+struct TabLdsU32 {
+  static constexpr bool kLds = true;
+  static constexpr bool kU32 = true;
+  typedef uint32_t pos_t;
+  volatile lds_u32* t;
+  struct Cell {
+    volatile lds_u32* p;
+    __device__ __forceinline__ operator uint32_t() const { return *p; }
+    __device__ __forceinline__ void operator=(uint32_t v) const { *p = v; }
+  };
+  __device__ __forceinline__ Cell operator[](uint32_t i) const { return Cell{t + i}; }
+};
+
+// table slot of a probe: v = its four bytes, b4 = the fifth in the low byte (byU32 only)
+template <typename Tab>
+__device__ __forceinline__ uint32_t probe_hash(uint32_t v, uint32_t b4) {
+  if constexpr (Tab::kU32) return hash5_12(v, b4);
+  else return hash13(v);
+}
 
 #ifndef S3S_FAST_STEPS
 #define S3S_FAST_STEPS 5  // measured: 3 -> 45.3, 5 -> 45.4 GB/s (TeraSort, two task threads), 21.2 vs 20.6 on wide rows
@@ -240,6 +281,8 @@ struct TabLds {
 //   is the highest lane of (same hash) & K below it, else cp.  One store commits K at the end.
 template <typename Src, bool kWindows, typename Tab = TabLds>
 __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* out, int lane) {
+  static_assert(!(kWindows && Tab::kU32), "the exact windows (16-bit candidates, same 4 bytes => same slot) are byU16 only");
+  typedef typename Tab::pos_t pos_t;
   const int mfl1 = len - kMfLimit + 1;  // mflimitPlusOne
   const int matchlimit = len - kLastLiterals;
   const int last4 = len - 4;
@@ -257,9 +300,26 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
 #endif
 
   if (len >= kMfLimit + 1) {
-    T[hash13(in.rd32(0))] = 0;  // LZ4_putPosition(ip = source); all lanes store the same value
+    // byU32 hashes five bytes: probes are loaded as 8 bytes (v, v4).  No hashed position lies above len - 12, so clamping
+    // the load to len - 8 moves no lane whose hash is used (and never reads past the chunk: it may end the allocation).
+    const int last8 = len - 8;
+    auto ld_probe = [&](int pos, uint32_t& v4) -> uint32_t {
+      if constexpr (Tab::kU32) {
+        const uint2 x = in.ld8(pos < last8 ? pos : last8);
+        v4 = x.y;
+        return x.x;
+      } else {
+        return in.rd32(pos < last4 ? pos : last4);
+      }
+    };
+    uint32_t vpre4 = 0, vput4 = 0;  // (byU32) the dwords behind vpre / vput
+    {
+      uint32_t v0_4 = 0;
+      const uint32_t v0 = Tab::kU32 ? ld_probe(0, v0_4) : in.rd32(0);
+      T[probe_hash<Tab>(v0, v0_4)] = 0;  // LZ4_putPosition(ip = source); all lanes store the same value
+    }
     int base = 1, t0 = 1;
-    uint32_t vpre = in.rd32(1 + lane < last4 ? 1 + lane : last4);  // prefetched v of the next batch
+    uint32_t vpre = ld_probe(1 + lane, vpre4);  // prefetched v of the next batch
     bool have_pre = true;
     uint32_t vput = 0;  // the 4 bytes at base-2, to insert before the batch (after a match)
     bool put_pending = false;
@@ -599,22 +659,36 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
       }
       nvalid = nvalid < kWave ? nvalid : kWave;
       const bool valid = lane < nvalid;
-      if (put_pending) T[hash13(vput)] = (uint16_t)(base - 2);  // LZ4_putPosition(ip - 2)
+      if (put_pending) T[probe_hash<Tab>(vput, vput4)] = (pos_t)(base - 2);  // LZ4_putPosition(ip - 2)
       put_pending = false;
-      const uint32_t v = have_pre ? vpre : in.rd32(pos < last4 ? pos : last4);
+      uint32_t v4 = vpre4;
+      const uint32_t v = have_pre ? vpre : ld_probe(pos, v4);
       have_pre = false;
-      const uint32_t h = hash13(v);
+      const uint32_t h = probe_hash<Tab>(v, v4);
       uint32_t c = 0, r = (uint32_t)pos;
       if (valid) {
         c = T[h];              // candidate as of the start of the batch
-        T[h] = (uint16_t)pos;  // speculative insert, all lanes at once
+        T[h] = (pos_t)pos;     // speculative insert, all lanes at once
         r = T[h];              // readback: did this lane own its slot?
       }
       const uint32_t w = in.rd32((int)c);
       const uint32_t vprev = __builtin_amdgcn_update_dpp(~v, v, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
       const uint64_t L = __ballot(r != (uint32_t)pos);              // lost its slot
-      const uint64_t M = __ballot(valid && w == v);                 // start-of-batch candidate matches
-      const uint64_t A = __ballot(valid && lane > 0 && v == vprev); // repeats the previous probe
+      uint64_t M, A;
+      if constexpr (Tab::kU32) {
+        // The probe has stored its position (above); a candidate more than 65 535 bytes back is then passed over WITHOUT a
+        // compare (LZ4_compress_generic: `if (matchIndex + LZ4_DISTANCE_MAX < current) continue`), equal bytes or not.  An
+        // empty slot reads as position 0 and falls under the same test.
+        M = __ballot(valid && c + 65535u >= (uint32_t)pos && w == v);
+        // "Repeats the previous probe": with five hashed bytes, equal FOUR bytes no longer mean the same slot.  The lane's
+        // true candidate is its predecessor exactly when the predecessor wrote THIS slot (same h) - the latest store before
+        // this probe - and it is a match when the four bytes agree; the offset is one step of the schedule, far below 65 535.
+        const uint32_t hprev = __builtin_amdgcn_update_dpp(~h, h, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
+        A = __ballot(valid && lane > 0 && v == vprev && h == hprev);
+      } else {
+        M = __ballot(valid && w == v);                 // start-of-batch candidate matches
+        A = __ballot(valid && lane > 0 && v == vprev); // repeats the previous probe
+      }
       // Clean prefix [0,B): lanes whose start-of-batch candidate is what the sequential code reads.
       // Everything below the smallest loser c0 is clean; c0 itself is clean iff its slot's winner is
       // a LATER lane (an earlier member of its hash group would have lost too).
@@ -641,9 +715,9 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
       }
       // table fix-up: winners the sequential code never reached restore the old entry, then
       // committed losers re-insert (c0, unless the adjacent match lane overrides the same slot)
-      if (valid && lane >= keep && r == (uint32_t)pos) T[h] = (uint16_t)c;
+      if (valid && lane >= keep && r == (uint32_t)pos) T[h] = (pos_t)c;
       const bool redo_c0 = clean0 && c0 < keep && !(adj && c0 == m - 1);
-      if ((redo_c0 && lane == c0) || (adj && lane == m)) T[h] = (uint16_t)pos;
+      if ((redo_c0 && lane == c0) || (adj && lane == m)) T[h] = (pos_t)pos;
 
       if (m < 0) {
         if (lim == nvalid && nvalid < kWave) break;  // ran into mflimit: last literals
@@ -662,8 +736,8 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
       const int ipe = ip0 + kMinMatch + fwd;  // first byte after the match
       // prefetch what the next batch needs while the sequence is being written out
       if (ipe < mfl1) {
-        vpre = in.rd32(ipe + lane < last4 ? ipe + lane : last4);
-        vput = in.rd32(ipe - 2);
+        vpre = ld_probe(ipe + lane, vpre4);
+        vput = Tab::kU32 ? ld_probe(ipe - 2, vput4) : in.rd32(ipe - 2);
         have_pre = true;
         put_pending = true;
       }
@@ -837,14 +911,50 @@ __global__ __launch_bounds__(kWave) void lz4_compress_l2_kernel(
 }
 
 
-// one wavefront per chunk, coalesced streaming (xxh32_wave): ~3x the 4-lanes-per-chunk kernel above
+// ---- byU32: chunks of kLz4U32From bytes and more (kItemLz4ChunkU32), one workgroup of one wavefront per item ----------
+// The same frame, slot and item_size as the kernel above, the general batch over the 4096 x u32 table.  No persistent
+// grid and no block touch: a chunk is 2 - 1024 times the 32 KiB one, so a launch per chunk is noise and a wavefront's
+// chunk no longer fits the share of L2 the touch was made for.  Items of every other kind are passed by.
+__global__ __launch_bounds__(kWave) void lz4_compress_u32_kernel(
+    const uint8_t* __restrict__ src, const Item* __restrict__ items, int32_t n_items, int32_t slot_stride,
+    const uint32_t* __restrict__ item_check, uint8_t* __restrict__ slots, uint32_t* __restrict__ item_size) {
+  __shared__ __attribute__((aligned(16))) uint32_t table[4096];
+  const int lane = threadIdx.x;
+  const int it = (int)blockIdx.x;
+  if (it >= n_items) return;
+  Item item = items[it];
+  {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)item.src_off);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)item.src_off >> 32));
+    item.src_off = (int64_t)(((uint64_t)hi << 32) | lo);
+    item.len = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)item.len);
+    item.kind = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)item.kind);
+    item.chunk = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)item.chunk);
+  }
+  if ((item.kind & 0xff) != kItemLz4ChunkU32) return;
+  {
+    uint4* tz = reinterpret_cast<uint4*>(table);
+    for (int i = lane; i < 16384 / 16; i += kWave) tz[i] = make_uint4(0, 0, 0, 0);
+  }
+  __syncthreads();
+  uint8_t* slot = slots + (size_t)item.chunk * (size_t)(uint32_t)slot_stride;
+  const uint32_t check = item_check[it];
+  const int clen = lz4_compress_wave<SrcGlobal, false, TabLdsU32>(SrcGlobal{src + item.src_off}, TabLdsU32{(lds_u32*)table},
+                                                                  item.len, slot + kSlotHeader, lane);
+  finish_frame(slot, item.len, clen, check, item.kind >> 8, item_size + it, lane);
+}
+
+
+// one wavefront per chunk, coalesced streaming (xxh32_wave): ~3x the 4-lanes-per-chunk kernel above.  kKind: the items it
+// hashes; for kItemLz4ChunkU32 it is the pre-pass (four lanes per chunk would be one chain of 64 Ki rounds on a 1 MiB chunk).
+template <int kKind>
 __global__ __launch_bounds__(kWave) void xxh32_items_wave_kernel(
     const uint8_t* __restrict__ src, const Item* __restrict__ items, int32_t n_items, uint32_t seed,
     uint32_t* __restrict__ item_check) {
   const int it = blockIdx.x;
   if (it >= n_items) return;
   const Item item = items[it];
-  if ((item.kind & 0xff) != kItemLz4Chunk) return;
+  if ((item.kind & 0xff) != kKind) return;
   const int lane = threadIdx.x;
   const uint32_t h = xxh32_wave(src + item.src_off, item.len, seed, lane);
   if (lane == 0) item_check[it] = h;
@@ -957,7 +1067,7 @@ __global__ __launch_bounds__(kWave) void xxh32_items_quad_kernel(
 
 void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                          uint32_t* d_item_check, uint8_t* d_slots, int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int resident_waves,
-                         int variant, hipStream_t st, hipEvent_t after_hash) {
+                         int variant, hipStream_t st, hipEvent_t after_hash, bool has_u32) {
   if (n_items <= 0) {
     if (after_hash) hipEventRecord(after_hash, st);
     return;
@@ -971,13 +1081,16 @@ void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_it
   static const int xxh_env = getenv("S3S_XXH") ? atoi(getenv("S3S_XXH")) : -1;
   const int xxh_mode = xxh_env >= 0 ? xxh_env : 2;
   if (xxh_mode == 0)
-    hipLaunchKernelGGL(xxh32_items_wave_kernel, dim3((unsigned)n_items), dim3(kWave), 0, st, d_src, d_items,
+    hipLaunchKernelGGL(xxh32_items_wave_kernel<kItemLz4Chunk>, dim3((unsigned)n_items), dim3(kWave), 0, st, d_src, d_items,
                        n_items, kLz4BlockSeed, d_item_check);
   else if (xxh_mode == 2)
     hipLaunchKernelGGL(xxh32_items_quad_kernel<false>, dim3((unsigned)((n_items + 15) / 16)), dim3(kWave), 0, st, d_src, d_items,
                        n_items, kLz4BlockSeed, d_item_check);
   else
     hipLaunchKernelGGL(xxh32_items_quad_kernel<true>, dim3((unsigned)((n_items + 15) / 16)), dim3(kWave), 0, st, d_src, d_items,
+                       n_items, kLz4BlockSeed, d_item_check);
+  if (has_u32)  // chunks of kLz4U32From bytes and more: one wavefront each
+    hipLaunchKernelGGL(xxh32_items_wave_kernel<kItemLz4ChunkU32>, dim3((unsigned)n_items), dim3(kWave), 0, st, d_src, d_items,
                        n_items, kLz4BlockSeed, d_item_check);
   if (after_hash) hipEventRecord(after_hash, st);
   // d_work: the launch's block counter (zeroed in stream order); resident_waves: 10 per CU
@@ -991,6 +1104,10 @@ void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_it
   else
     hipLaunchKernelGGL(lz4_compress_l2_kernel<true>, dim3((unsigned)grid), dim3(kWave), 0, st, d_src,
                        d_items, n_items, slot_stride, d_item_check, d_slots, d_item_size, d_work);
+  // the byU32 chunks: the kernels above pass them by (their kind), this one passes everything else by
+  if (has_u32)
+    hipLaunchKernelGGL(lz4_compress_u32_kernel, dim3((unsigned)n_items), dim3(kWave), 0, st, d_src, d_items, n_items,
+                       slot_stride, d_item_check, d_slots, d_item_size);
 }
 
 }  // namespace s3s

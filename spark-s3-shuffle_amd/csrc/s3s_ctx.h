@@ -154,6 +154,10 @@ inline int lz4_level(int64_t block_size) {
   return level < 0 ? 0 : level;
 }
 
+// plan record kind of an LZ4 chunk: liblz4 picks its parse by the input's LENGTH (LZ4_64Klimit), not by the block size, so a
+// partition's tail below kLz4U32From bytes is a byU16 chunk whatever the block size
+inline int32_t lz4_chunk_kind(int32_t len) { return len >= kLz4U32From ? kItemLz4ChunkU32 : kItemLz4Chunk; }
+
 inline int64_t snappy_max_len(int64_t n) { return 32 + n + n / 6; }
 
 // ---- Snappy chunks and their plan records --------------------------------------------------------------------------

@@ -18,10 +18,12 @@ namespace s3s {
 
 constexpr int kWave = 64;
 constexpr int kMaxBlock = 32768;          // largest codec chunk the LDS-resident kernels take (Snappy; LZ4's default)
-constexpr int kLz4MaxBlock = 65536;       // largest LZ4 chunk of the map side (round 4): liblz4 parses inputs below 65 547 bytes
-                                          // with the SAME 8192 x u16 table (byU16) - positions just need all 16 bits - so the
-                                          // window engine takes them as it is; from 64 KiB + 11 on liblz4 switches to its
-                                          // 4096 x u32 table with a 5-byte hash: another parse, not built
+constexpr int kLz4MaxBlock = 65536;       // largest LZ4 block size S3S_OPT_LZ4_BLOCK_SIZE takes (round 4): liblz4 parses inputs below
+                                          // 65 547 bytes with the SAME 8192 x u16 table (byU16) - positions just need all 16 bits - so
+                                          // the window engine takes them as it is.  Larger blocks are S3S_OPT_LZ4_BLOCK_SIZE_LARGE
+                                          // (ABI 10, up to kBatchMaxBlock)
+constexpr int kLz4U32From = 65536 + 11;   // LZ4_64Klimit: from this chunk LENGTH on liblz4 parses with its 4096 x u32 table, a 5-byte
+                                          // hash and a distance test (byU32): kItemLz4ChunkU32, lz4_compress_u32_kernel
 constexpr int kBatchMaxBlock = 1 << 25;   // largest LZ4Block frame the batch decoder takes (lz4-java's MAX_BLOCK_SIZE); also the
                                           // largest Snappy chunk of both sides (spark.io.compression.snappy.blockSize, ABI 9)
 constexpr int kSnappyFragment = 65536;    // snappy::RawCompress compresses its input in independent 64 KiB fragments
@@ -39,7 +41,11 @@ enum : int32_t {
   // a Snappy chunk above one fragment (ABI 9): a head item, then one kItemSnappyFrag item per 64 KiB fragment, in order
   kItemSnappyChunkHead = 4,  // i32 BE length + varint32(len); len = the whole chunk.  Its size is known from len; the
                              // length VALUE is the sum of the fragments' sizes, written by the gather (assemble.hip)
-  kItemSnappyFrag = 5        // one fragment's raw snappy elements (no preamble), compressed on its own wavefront
+  kItemSnappyFrag = 5,       // one fragment's raw snappy elements (no preamble), compressed on its own wavefront
+  // an LZ4Block data frame whose chunk is kLz4U32From bytes or longer (ABI 10): the same frame, slot and item_size as
+  // kItemLz4Chunk, parsed by the byU32 kernel.  A kind of its own, so that the kernels of the <= 64 KiB path pass it by
+  // without a length test of their own.
+  kItemLz4ChunkU32 = 6
 };
 
 // bytes of snappy's varint32 preamble of a block of n bytes
@@ -64,9 +70,11 @@ constexpr uint32_t kRawFlag = 0x80000000u;
 //   variant 0: chunk staged in LDS (3 wavefronts/CU); 1: chunk read through L1/L2 (10/CU);
 //   2: as 1 plus the window-speculative parse (default)
 //   slot_stride: bytes between slots (kSlotHeader + the block size rounded up to 16)
+//   has_u32: the items may hold kItemLz4ChunkU32 records (block size >= kLz4U32From): their hash pass and the byU32 parse
+//   are two more launches over the same items
 void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                          uint32_t* d_item_check, uint8_t* d_slots, int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int resident_waves,
-                         int variant, hipStream_t st, hipEvent_t after_hash = nullptr);
+                         int variant, hipStream_t st, hipEvent_t after_hash = nullptr, bool has_u32 = false);
 // Snappy: same for kItemSnappyChunk.
 bool snappy_compress_available();
 //   slot_stride: bytes between slots (a raw snappy block can be larger than its chunk)

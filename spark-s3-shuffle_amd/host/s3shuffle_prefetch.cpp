@@ -126,11 +126,17 @@ struct CtxKey {
 };
 std::mutex g_ctxMu;
 std::multimap<CtxKey, s3s_ctx*> g_ctxIdle;
+// the option that carries the codec's block size: LZ4 blocks above 64 KiB are the caller's explicit choice (ABI 10, key 8)
+int blockSizeKey(const Conf& cf) {
+  if (!cf.compress) return 0;
+  if (cf.codec == "snappy") return S3S_OPT_SNAPPY_BLOCK_SIZE;
+  return cf.blockSize > 65536 ? S3S_OPT_LZ4_BLOCK_SIZE_LARGE : S3S_OPT_LZ4_BLOCK_SIZE;
+}
 }  // namespace
 
 s3s_ctx* acquireContext(const S3ShuffleDispatcher& d, int device) {
   const Conf& cf = d.conf();
-  const CtxKey key{device, !cf.compress ? 0 : (cf.codec == "snappy" ? S3S_OPT_SNAPPY_BLOCK_SIZE : S3S_OPT_LZ4_BLOCK_SIZE),
+  const CtxKey key{device, blockSizeKey(cf),
                    cf.compress ? (int64_t)cf.blockSize : 0};
   {
     std::lock_guard<std::mutex> lk(g_ctxMu);
@@ -154,7 +160,7 @@ s3s_ctx* acquireContext(const S3ShuffleDispatcher& d, int device) {
 void releaseContext(const S3ShuffleDispatcher& d, int device, s3s_ctx* c) {
   if (!c) return;
   const Conf& cf = d.conf();
-  const CtxKey key{device, !cf.compress ? 0 : (cf.codec == "snappy" ? S3S_OPT_SNAPPY_BLOCK_SIZE : S3S_OPT_LZ4_BLOCK_SIZE),
+  const CtxKey key{device, blockSizeKey(cf),
                    cf.compress ? (int64_t)cf.blockSize : 0};
   std::lock_guard<std::mutex> lk(g_ctxMu);
   g_ctxIdle.emplace(key, c);

@@ -18,6 +18,7 @@ OPT_LZ4_VARIANT = 4
 OPT_LZ4_DECODE_VARIANT = 5
 OPT_SNAPPY_VARIANT = 6
 OPT_LZ4_VARIANT_USED = 7
+OPT_LZ4_BLOCK_SIZE_LARGE = 8  # ABI 10: spark.io.compression.lz4.blockSize 64 .. 32m (key 1 stops at 64k and keeps doing so)
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
 STATUS_NOT_RUN = -100  # per-entry status of a batch call that failed as a call before this entry had a verdict (ABI 6)
