@@ -56,6 +56,13 @@
  * Ownership: the caller owns every buffer passed in; the library owns only the ctx.
  * Errors: 0 on success, negative S3S_E_* otherwise; never aborts; s3s_last_error() gives
  * a message.  There is NO CPU fallback: without a usable HIP device s3s_create() fails.
+ * Sizes: every offset, length and capacity is a full int64_t - a map output, a fetched range, a
+ * checksum range or the sum of a batch may lie far above 4 GiB (tested: sources and images above
+ * 2^32 + 64 MiB through the device entry points, offsets around 2^31 and 2^32 and buffers that
+ * straddle a 4 GiB-aligned address in every kernel).  What is limited is the COUNT of pieces of one
+ * call: more than 0x7fffff00 codec blocks, frames or 16 KiB checksum segments is S3S_E_UNSUPPORTED,
+ * answered before anything is allocated or launched where the count follows from the arguments
+ * alone (the compress entry points, s3s_decompress_range_device).
  */
 #ifndef S3SHUFFLE_CODEC_H
 #define S3SHUFFLE_CODEC_H

@@ -45,11 +45,20 @@ __device__ __forceinline__ uint32_t multmodp(uint32_t a, uint32_t b, uint32_t po
   return p;
 }
 
-// x^(8n) mod P
+// x^(8n) mod P; x2n[k] = x^(2^k), k < 32.  zlib wraps that table (x2n[k & 31]) because x^(2^32) = x modulo ITS polynomial, which
+// is irreducible.  CRC-32C's is not - it is (x + 1) times a polynomial of degree 31, and x^(2^32) = x^2 there - so from
+// n = 2^29 bytes on (a range of 512 MiB and more) the powers are squared on from the table's last entry instead.
 __device__ __forceinline__ uint32_t x8n(const uint32_t* x2n, uint64_t n, uint32_t poly) {
   uint32_t p = 0x80000000u;
-  for (int k = 3; n; n >>= 1, k++)
-    if (n & 1) p = multmodp(x2n[k & 31], p, poly);
+  for (int k = 3; n && k < 32; n >>= 1, k++)
+    if (n & 1) p = multmodp(x2n[k], p, poly);
+  if (n) {
+    uint32_t sq = x2n[31];
+    for (; n; n >>= 1) {
+      sq = multmodp(sq, sq, poly);
+      if (n & 1) p = multmodp(sq, p, poly);
+    }
+  }
   return p;
 }
 

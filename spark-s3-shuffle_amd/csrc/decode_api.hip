@@ -176,6 +176,11 @@ int s3s_decompress_range_device(s3s_ctx* ctx, int codec, int checksum_algo, cons
   }
 
   const int32_t n = nparts;
+  if (checksum_algo != S3S_CHECKSUM_NONE) {  // a range of too many checksum segments is refused before anything is allocated or launched
+    int64_t segs = 0;
+    for (int32_t p = 0; p < n; p++) segs += worst_segs(part_offsets[p + 1] - part_offsets[p]);
+    if (segs > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "range too large for one call");
+  }
   const int32_t n_tiles = codec == S3S_CODEC_LZ4 ? lz4_tile_count(comp_len) : 0;
   // pinned staging: [offsets n+1][seg_start n+1][sums n][misc 8 x int64]
   const size_t off_bytes = sizeof(int64_t) * (size_t)(n + 1), seg_bytes = sizeof(int32_t) * (size_t)(n + 1);
@@ -200,7 +205,6 @@ int s3s_decompress_range_device(s3s_ctx* ctx, int codec, int checksum_algo, cons
       h_off[p] = part_offsets[p];
       h_seg[p] = (int32_t)segs;
       segs += worst_segs(part_offsets[p + 1] - part_offsets[p]);
-      if (segs > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "range too large for one call");
     }
     h_off[n] = part_offsets[n];
     h_seg[n] = (int32_t)segs;

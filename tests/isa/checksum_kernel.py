@@ -58,20 +58,22 @@ def _program(needle):
     return _PROG[needle]
 
 
-def checksum_ranges(algo, data: bytes, offsets, data_len=None, fold_group=0):
+def checksum_ranges(algo, data: bytes, offsets, data_len=None, fold_group=0, far=0, cross=None):
     """algo 1 = Adler32, 2 = CRC32, 3 = CRC32C (the CRC32 kernels on the other polynomial's tables, as
     launch_checksum_with_tables picks them); offsets: n + 1 ascending positions into data.  -> list of n checksums.
     fold_group = G > 0: the two-level form for ranges of very many segments (checksum_fold_kernel over groups of G segments,
     then the combine kernel over groups) — the product folds 256 segments from 2 048 per range on; a small G exercises the
-    same code on ranges the interpreter can afford."""
-    offsets = np.asarray(offsets, np.int64)
+    same code on ranges the interpreter can afford.
+    far = K: the kernels get `data - K`, offsets + K and data_len + K (the same bytes, offset arithmetic around K);
+    cross = {"data": byte}: gfx950_emu.Memory(cross)."""
+    offsets = np.asarray(offsets, np.int64) + far
     n = len(offsets) - 1
     seg_start = np.zeros(n + 1, np.int32)
     for p in range(n):
         seg_start[p + 1] = seg_start[p] + (int(offsets[p + 1] - offsets[p]) + SEG - 1) // SEG
     total = int(seg_start[n])
-    mem = emu.Memory()
-    a_data = mem.map(np.frombuffer(bytearray(data) or bytearray(1), dtype=np.uint8), "data", writable=False)
+    mem = emu.Memory(cross)
+    a_data = mem.map(np.frombuffer(bytearray(data) or bytearray(1), dtype=np.uint8), "data", writable=False) - far
     a_off = mem.map(offsets, "offsets", writable=False)
     a_seg = mem.map(seg_start, "seg_start", writable=False)
     a_tab = mem.map(tables(0x82F63B78 if algo == 3 else 0xEDB88320), "tables", writable=False)
@@ -80,7 +82,7 @@ def checksum_ranges(algo, data: bytes, offsets, data_len=None, fold_group=0):
     a_par = mem.map(partial if total else np.zeros(1, np.uint32), "partial")
     out = np.full(n, -1, np.int64)
     a_out = mem.map(out, "out")
-    dl = len(data) if data_len is None else data_len
+    dl = (len(data) if data_len is None else data_len) + far
     tag = "checksum_segments_kernelILi%dE" % algo
     if total:
         prog, entry = _program(tag)

@@ -35,19 +35,23 @@ def program(fmt, flags=(), kernel="batch"):
     return _PROGS[key]
 
 
-def decode_blocks(blocks, fmt=0, methods=None, profile=None, flags=(), grid=None, kernel="batch", checks=None):
+def decode_blocks(blocks, fmt=0, methods=None, profile=None, flags=(), grid=None, kernel="batch", checks=None, far=None, cross=None):
     """blocks: list of (payload bytes, decoded length).  fmt 0 = LZ4 block payloads, 1 = raw Snappy blocks.
     Returns (list of decoded bytes, status word, waves).  flags: extra -D macros of an experiment build.  checks: the frames' LZ4Block check fields (the LZ4 ring kernel verifies
-    xxHash32 itself; the batch decoder leaves that to lz4_verify_frames_kernel)."""
+    xxHash32 itself; the batch decoder leaves that to lz4_verify_frames_kernel).
+    far = {"comp": K, "dst": K}: the kernel gets `comp - K` with Frame.comp_off + K and `dst - K` with frame_out[] + K (the same
+    bytes, offset arithmetic around K); cross = {region name: byte}: gfx950_emu.Memory(cross)."""
     prog, entry, text, lds = program(fmt, flags, kernel)
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
+    far = far or {}
+    k_comp, k_dst = far.get("comp", 0), far.get("dst", 0)
     comp = b"".join(p for p, _ in blocks)
     frames = bytearray()
     outs = []
     co = oo = 0
     for k, (p, olen) in enumerate(blocks):
         method = (methods[k] if methods else (0x20 if fmt == 0 else 1))
-        frames += struct.pack("<qiiIi", co, len(p), olen, checks[k] if checks else 0, method)
+        frames += struct.pack("<qiiIi", co + k_comp, len(p), olen, checks[k] if checks else 0, method)
         outs.append(oo)
         co += len(p)
         oo += olen
@@ -58,10 +62,10 @@ def decode_blocks(blocks, fmt=0, methods=None, profile=None, flags=(), grid=None
         # around the buffer's last byte is touched as a whole (never a byte outside it — an allocation is a multiple of 4).
         # The filler is not zero, so a decoder that USED those bytes would decode wrongly.
         comp = comp + b"\xEE" * (-len(comp) % 4)
-    a_comp = mem.map(np.frombuffer(bytearray(comp) or bytearray(1), dtype=np.uint8), "comp", writable=False)
+    a_comp = mem.map(np.frombuffer(bytearray(comp) or bytearray(1), dtype=np.uint8), "comp", writable=False) - k_comp
     a_frames = mem.map(np.frombuffer(frames, dtype=np.uint8), "frames", writable=False)
-    a_fout = mem.map(np.array(outs + [oo], dtype=np.int64), "frame_out", writable=False)
-    a_dst = mem.map(dst, "dst")
+    a_fout = mem.map(np.array(outs + [oo], dtype=np.int64) + k_dst, "frame_out", writable=False)
+    a_dst = mem.map(dst, "dst") - k_dst
     a_status = mem.map(status, "status")
     kernarg = struct.pack("<QQiiQQQ", a_comp, a_frames, len(blocks), 0, a_fout, a_dst, a_status)
     objs = emu.parse_objects(text)
@@ -71,25 +75,28 @@ def decode_blocks(blocks, fmt=0, methods=None, profile=None, flags=(), grid=None
     return res, int(status[0]), waves
 
 
-def decode_range(comp: bytes, recs, outs, verify=True, fmt=0):
+def decode_range(comp: bytes, recs, outs, verify=True, fmt=0, far=None, cross=None):
     """The decode launches of one fetched range: `recs` / `outs` = the frame records and output offsets the compiled frame
     discovery produced (tests/isa/discover_kernel.py), batch_decode_kernel<LZ4> over them, then lz4_verify_frames_kernel
     (xxHash32 of every decoded block against the frame's check field).  Buffers of exactly their sizes.
-    -> (status, decoded bytes)"""
+    -> (status, decoded bytes).  far = {"comp": K, "dst": K} / cross: as decode_blocks (`recs` as the discovery wrote them:
+    K is added to their comp_off here)."""
+    far = far or {}
+    k_comp, k_dst = far.get("comp", 0), far.get("dst", 0)
     prog, entry, text, lds = program(fmt)
     verify = verify and fmt == 0  # (Snappy chunks carry no check field: the partition checksum is their guard)
     n = len(recs)
     total = outs[-1]
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
     frames = bytearray()
     for r in recs:
-        frames += struct.pack("<qiiIi", *r)
+        frames += struct.pack("<qiiIi", r[0] + k_comp, *r[1:])
     dst = np.zeros(max(total, 1), dtype=np.uint8)[:total]
     status = np.zeros(4, dtype=np.int32)
-    a_comp = mem.map(np.frombuffer(bytearray(comp), dtype=np.uint8), "comp", writable=False)
+    a_comp = mem.map(np.frombuffer(bytearray(comp), dtype=np.uint8), "comp", writable=False) - k_comp
     a_frames = mem.map(np.frombuffer(frames or bytearray(24), dtype=np.uint8), "frames", writable=False)
-    a_fout = mem.map(np.array(outs, dtype=np.int64), "frame_out", writable=False)
-    a_dst = mem.map(dst if total else np.zeros(1, np.uint8), "dst")
+    a_fout = mem.map(np.array(outs, dtype=np.int64) + k_dst, "frame_out", writable=False)
+    a_dst = mem.map(dst if total else np.zeros(1, np.uint8), "dst") - k_dst
     a_status = mem.map(status, "status")
     objs = {k: v for k, v in emu.parse_objects(text).items() if k.startswith("_ZN3s3s")}
     if n:

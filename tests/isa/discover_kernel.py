@@ -46,14 +46,15 @@ def _launch(needle, mem, kernarg, grid):
     emu.launch(prog, entry, mem, kernarg, grid, 0, objects=_PROG["objs"])
 
 
-def discover(stream: bytes):
+def discover(stream: bytes, cross=None):
     """-> (status, frames) with frames = [(payload offset, payload bytes, decoded bytes, check, method)], and the
-    exclusive scan of the decoded sizes (n_frames + 1 entries) the decode launch uses as output offsets."""
+    exclusive scan of the decoded sizes (n_frames + 1 entries) the decode launch uses as output offsets.
+    cross = {"comp": byte}: gfx950_emu.Memory(cross) (the tiles are k * 65536 from the range start: what moves is the range)."""
     n = len(stream)
     n_tiles = (n + TILE - 1) // TILE
     if n_tiles == 0:
         return 0, [], [0]
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
     a_comp = mem.map(np.frombuffer(bytearray(stream), dtype=np.uint8), "comp", writable=False)
     spec_entry = np.full(n_tiles, -7, np.int64)
     spec_exit = np.full(n_tiles, -7, np.int64)
@@ -101,12 +102,14 @@ def reference_frames(stream: bytes):
     return out
 
 
-def discover_snappy(stream: bytes, part_offsets, chunk_format=0):
-    """chunk_format 1: compress-lzf chunk chains (LZFInputStream) through the same two kernels (round 4).
+def discover_snappy(stream: bytes, part_offsets, chunk_format=0, far=0, cross=None):
+    """far = K: the kernels get `comp - K` and part_offsets + K, and write Frame.comp_off + K (returned with K taken off again);
+    cross = {"comp": byte}: gfx950_emu.Memory(cross).
+    chunk_format 1: compress-lzf chunk chains (LZFInputStream) through the same two kernels (round 4).
     SnappyOutputStream images of several partitions in one range (csrc/snappy_decompress.hip: snappy_count_kernel ->
     scan_u32_kernel -> snappy_emit_kernel -> scan_u32_kernel, as decode_api.hip launches them).
     -> (status, frames [(payload offset, payload bytes, decoded bytes, 0, 1)], output offsets)"""
-    offs = np.asarray(part_offsets, np.int64)
+    offs = np.asarray(part_offsets, np.int64) + far
     n_parts = len(offs) - 1
     if "sn" not in _PROG:
         text = lk.compile_asm("snappy_decompress.hip")
@@ -120,8 +123,8 @@ def discover_snappy(stream: bytes, part_offsets, chunk_format=0):
         entry = lk.find_kernel(text, needle)
         emu.launch(emu.Program(text, entry), entry, mem, kernarg, grid, 0, objects=objs)
 
-    mem = emu.Memory()
-    a_comp = mem.map(np.frombuffer(bytearray(stream) or bytearray(1), dtype=np.uint8), "comp", writable=False)
+    mem = emu.Memory(cross)
+    a_comp = mem.map(np.frombuffer(bytearray(stream) or bytearray(1), dtype=np.uint8), "comp", writable=False) - far
     a_off = mem.map(offs, "part_off", writable=False)
     cnt = np.full(n_parts, 0xFFFFFFFF, np.uint32)
     base = np.full(n_parts + 1, -7, np.int64)
@@ -141,20 +144,22 @@ def discover_snappy(stream: bytes, part_offsets, chunk_format=0):
     run("snappy_emit_kernel", struct.pack("<QQiiQQQQi", a_comp, a_off, n_parts, 0, a_base, a_fr, a_or, a_st, chunk_format), (n_parts + 63) // 64)
     _launch("scan_u32_kernel", mem, struct.pack("<QqQ", a_or, n_frames, a_fo), 1)
     recs = [struct.unpack_from("<qiiIi", frames, 24 * k) for k in range(n_frames)]
+    recs = [(r[0] - far,) + r[1:] for r in recs]
     return int(status[0]), recs, [int(x) for x in fout]
 
 
-def decode_ranges_batch(ranges, capacities, skip=()):
+def decode_ranges_batch(ranges, capacities, skip=(), cross=None):
     """The batched reduce-side call for LZ4 (s3s_decompress_ranges_batch_device, csrc/decode_api.hip) through the compiled
     kernels: tile_speculate_batch -> tile_resolve_batch | host: frame counts -> tile_emit_batch -> frames_finish_batch ->
     ONE batch_decode_kernel launch over the frames of every range (comp = dst = nullptr: the records carry absolute
     addresses) -> lz4_verify_frames_kernel.  ranges: list of LZ4Block streams (bytes); capacities: destination bytes per range
     (the destination buffer of a range has exactly that size); skip: ranges the host marks as failed (checksum) beforehand.
-    -> list of (status, decoded bytes or None) per range, and the decode launch's own status word"""
+    -> list of (status, decoded bytes or None) per range, and the decode launch's own status word
+    cross = {"comp0": byte, "dst1": byte, ...}: gfx950_emu.Memory(cross) (the regions of range r are comp<r> and dst<r>)"""
     import decode_kernel as dk
 
     n_ranges = len(ranges)
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
     desc, bufs = [], []
     tile_range = []
     status = np.zeros(n_ranges + 1, np.int32)

@@ -41,15 +41,37 @@ def s64(x):
 class Memory:
     """Flat 64-bit address space made of named regions; every access is bounds-checked."""
 
-    def __init__(self):
+    CROSS_BASE = 0x7F1000000000  # regions placed through `cross` sit here, 8 GiB apart (the default ones start at 0x7F0000000000)
+
+    def __init__(self, cross=None):
+        """cross: {region name: byte index}: the region of that name is mapped so that this byte of it has a 4 GiB-aligned
+        address (the low dword of the addresses wraps from 0xFFFFFFxx to 0x000000xx inside the buffer)"""
         self.regions = []
         self.next_base = 0x7F0000000000
+        self.cross = dict(cross or {})
+        self.crossed = {}
 
-    def map(self, data, name, writable=True, guard=1 << 24):
+    def map(self, data, name, writable=True, guard=1 << 24, base=None):
+        """base: an explicit address for the region (default: the next free 64 KiB-aligned one); a region that overlaps an
+        existing one is an error"""
         arr = data if isinstance(data, np.ndarray) else np.frombuffer(bytearray(data), dtype=np.uint8)
         arr = arr.view(np.uint8).reshape(-1)
-        base = self.next_base
-        self.next_base += ((arr.size + guard + 0xFFFF) >> 16) << 16
+        if base is None and name in self.cross:
+            at = int(self.cross[name])
+            if not 0 <= at <= arr.size:
+                raise EmuError("crossing at byte %d lies outside region %s (%d bytes)" % (at, name, arr.size))
+            base = self.CROSS_BASE + (len(self.crossed) << 33) - at
+            self.crossed[name] = base
+        if base is None:
+            base = self.next_base
+            self.next_base += ((arr.size + guard + 0xFFFF) >> 16) << 16
+        else:
+            base = int(base)
+            if base <= 0 or base + arr.size > 1 << 63:
+                raise EmuError("region %s: base 0x%x is outside the address space" % (name, base))
+        for b, a, nm, _ in self.regions:
+            if base < b + max(a.size, 1) and b < base + max(arr.size, 1):
+                raise EmuError("region %s at 0x%x overlaps region %s at 0x%x" % (name, base, nm, b))
         self.regions.append((base, arr, name, writable))
         return base
 
@@ -1565,6 +1587,14 @@ class Program:
         w.wv32(i.ops[0], (a * b + c).astype(np.float32).view(np.uint32))  # (double product + add, rounded once)
 
     x_v_mad_f32 = x_v_fma_f32
+
+    def x_v_fmamk_f32(self, w, i):  # D = S0 * K + S1 (the literal K is the third operand): hipcc's 64-bit division, whose
+        a, k, c = (self._f32(w, o).astype(np.float64) for o in i.ops[1:4])  # operands have a non-zero high dword
+        w.wv32(i.ops[0], (a * k + c).astype(np.float32).view(np.uint32))
+
+    def x_v_fmaak_f32(self, w, i):  # D = S0 * S1 + K (the literal K is the last operand)
+        a, b, k = (self._f32(w, o).astype(np.float64) for o in i.ops[1:4])
+        w.wv32(i.ops[0], (a * b + k).astype(np.float32).view(np.uint32))
 
     def x_v_cmp_ge_f32(self, w, i):
         w.wmask(i.ops[0], self._f32(w, i.ops[1]) >= self._f32(w, i.ops[2]))

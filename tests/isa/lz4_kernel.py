@@ -65,26 +65,32 @@ def program(windows=True, flags=()):
     return _PROGS[key]
 
 
-def compress_chunks(chunks, windows=True, flags=(), profile=None, lds_order=None, tail_guard=0, hooks=None, block=32768):
+def compress_chunks(chunks, windows=True, flags=(), profile=None, lds_order=None, tail_guard=0, hooks=None, block=32768, far=None,
+                    cross=None):
     """chunks: list of uint8 arrays (<= block bytes each; block <= 65536: the slot stride the host passes is 32 + block).  The source buffer ends exactly at the last chunk's
-    last byte (+ tail_guard), so any read past a chunk that ends the allocation faults."""
+    last byte (+ tail_guard), so any read past a chunk that ends the allocation faults.
+    far = {"src": K, "slots": K}: the kernel gets `src - K` with Item.src_off + K, and `slots - chunk0 * stride` with
+    Item.chunk from chunk0 on (the first slot whose byte offset lies above K); cross = {region name: byte}: gfx950_emu.Memory(cross)."""
     prog, entry = program(windows, flags)
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
+    far = far or {}
+    k_src = far.get("src", 0)
     src = np.concatenate([np.asarray(c, dtype=np.uint8) for c in chunks] + [np.zeros(tail_guard, np.uint8)])
     n = len(chunks)
     items = bytearray()
-    off = 0
-    for k, c in enumerate(chunks):
-        items += struct.pack("<qiiii", off, len(c), 0 | (5 << 8), k, 0)
-        off += len(c)
+    off = k_src
     K_SLOT_BYTES = K_SLOT_HEADER + ((block + 15) & ~15)
+    ch0 = far.get("slots", 0) // K_SLOT_BYTES + 1 if far.get("slots", 0) else 0
+    for k, c in enumerate(chunks):
+        items += struct.pack("<qiiii", off, len(c), 0 | (5 << 8), ch0 + k, 0)
+        off += len(c)
     slots = np.zeros(n * K_SLOT_BYTES, dtype=np.uint8)
     sizes = np.zeros(n, dtype=np.uint32)
     checks = np.arange(n, dtype=np.uint32) * np.uint32(0x01010101)
-    a_src = mem.map(src if src.size else np.zeros(1, np.uint8), "src", writable=False)
+    a_src = mem.map(src if src.size else np.zeros(1, np.uint8), "src", writable=False) - k_src
     a_items = mem.map(np.frombuffer(items, dtype=np.uint8), "items", writable=False)
     a_check = mem.map(checks, "item_check", writable=False)
-    a_slots = mem.map(slots, "slots")
+    a_slots = mem.map(slots, "slots") - ch0 * K_SLOT_BYTES
     a_sizes = mem.map(sizes, "item_size")
     # The kernel is a persistent grid (every wavefront takes blocks from a counter until none is left); the interpreter
     # runs wavefronts one after the other, so each chunk gets its own one-item launch and its own wavefront's statistics

@@ -71,15 +71,26 @@ def _compress(mem, a_src, items, n_items, a_slots, stride, a_size, windows):
     return a_items
 
 
-def compress_map_output(parts, block, dst_bytes, windows=True):
-    """parts: list of bytes (one per partition).  -> (status, .data image, index list [n + 1])"""
+def _far(far, stride):
+    far = far or {}
+    k = far.get("slots", 0)
+    return far.get("src", 0), k // stride + 1 if k else 0, far.get("dst", 0)
+
+
+def compress_map_output(parts, block, dst_bytes, windows=True, far=None, cross=None):
+    """parts: list of bytes (one per partition).  -> (status, .data image, index list [n + 1])
+    far = {"src": K, "slots": K, "dst": K}: the kernels get `pointer - K` and every 64-bit offset they add to it is `+ K`
+    (Item.src_off; Item.chunk from the first slot whose byte offset lies above K; item_off patched between scan and gather,
+    dst_capacity + K); cross = {region name: byte}: gfx950_emu.Memory(cross)."""
     n = len(parts)
     stride = slot_stride(block)
-    items, part_first, total, n_slots = _plan(parts, block)
+    k_src, ch0, k_dst = _far(far, stride)
+    items, part_first, total, n_slots = _plan(parts, block, k_src, ch0)
+    n_slots -= ch0
     n_items = len(items) // 24
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
     src = np.frombuffer(b"".join(parts), dtype=np.uint8)
-    a_src = mem.map(src.copy() if src.size else np.zeros(1, np.uint8), "src", writable=False)
+    a_src = mem.map(src.copy() if src.size else np.zeros(1, np.uint8), "src", writable=False) - k_src
     size = np.zeros(max(n_items, 1), np.uint32)
     item_off = np.full(n_items + 1, -7, np.int64)
     index = np.full(n + 1, -7, np.int64)
@@ -87,27 +98,29 @@ def compress_map_output(parts, block, dst_bytes, windows=True):
     status = np.zeros(1, np.int32)
     dst = np.full(max(dst_bytes, 1), 0xA5, np.uint8)[:dst_bytes]
     a_size, a_off, a_index = mem.map(size, "item_size"), mem.map(item_off, "item_off"), mem.map(index, "index")
-    a_slots, a_status = mem.map(slots, "slots"), mem.map(status, "status")
+    a_slots, a_status = mem.map(slots, "slots") - ch0 * stride, mem.map(status, "status")
     a_pf = mem.map(np.array(part_first, np.int32), "part_first", writable=False)
-    a_dst = mem.map(dst if dst_bytes else np.zeros(1, np.uint8), "dst")
+    a_dst = mem.map(dst if dst_bytes else np.zeros(1, np.uint8), "dst") - k_dst
     a_items = _compress(mem, a_src, items, n_items, a_slots, stride, a_size, windows) if n_items else 0
     prog, entry, objs = _prog("assemble.hip", "scan_items_kernel")
     emu.launch(prog, entry, mem, struct.pack("<QiiQQiiQ", a_size, n_items, 0, a_off, a_pf, n, 0, a_index), 1, 0, objects=objs)
+    item_off += k_dst
     if n_items:
         prog, entry, objs = _prog("assemble.hip", "gather_items_kernel")
         emu.launch(prog, entry, mem, struct.pack("<QQiiQqQQQqQ", a_src, a_items, n_items, 0, a_slots, stride, a_size, a_off,
-                                                 a_dst, dst_bytes, a_status), n_items, 0, block_x=256, objects=objs)
+                                                 a_dst, dst_bytes + k_dst, a_status), n_items, 0, block_x=256, objects=objs)
     return int(status[0]), dst.tobytes(), [int(x) for x in index]
 
 
-def compress_map_outputs_batch(tasks, block, dst_bytes_per_task, windows=True):
+def compress_map_outputs_batch(tasks, block, dst_bytes_per_task, windows=True, far=None, cross=None):
     """A batched Snappy map-side call: ONE compress launch over the items of every task, then the tail kernels once per
     call through TaskTail descriptors.  -> list of (status, image, index) per task."""
     T = len(tasks)
     stride = slot_stride(block)
     items = bytearray()
     pf_all, first_item, first_part, n_parts = [], [], [], []
-    off = slot = 0
+    k_src, ch0, k_dst = _far(far, stride)  # (as compress_map_output; "dst" shifts every task's TaskTail.dst: regions dst0, dst1, ...)
+    off, slot = k_src, ch0
     for parts in tasks:
         first_item.append(len(items) // 24)
         first_part.append(sum(n_parts))
@@ -118,9 +131,10 @@ def compress_map_outputs_batch(tasks, block, dst_bytes_per_task, windows=True):
     n_items = len(items) // 24
     first_item.append(n_items)
     total_parts = sum(n_parts)
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
+    slot -= ch0
     src = np.frombuffer(b"".join(b"".join(p) for p in tasks), dtype=np.uint8)
-    a_src = mem.map(src.copy() if src.size else np.zeros(1, np.uint8), "src", writable=False)
+    a_src = mem.map(src.copy() if src.size else np.zeros(1, np.uint8), "src", writable=False) - k_src
     size = np.zeros(max(n_items, 1), np.uint32)
     item_off = np.full(n_items + T + 1, -7, np.int64)
     index = np.full(total_parts + T, -7, np.int64)
@@ -129,16 +143,17 @@ def compress_map_outputs_batch(tasks, block, dst_bytes_per_task, windows=True):
     dsts = [np.full(max(n, 1), 0xA5, np.uint8)[:n] for n in dst_bytes_per_task]
     a_dsts = [mem.map(d if d.size else np.zeros(1, np.uint8), "dst%d" % t) for t, d in enumerate(dsts)]
     a_size, a_off, a_index = mem.map(size, "item_size"), mem.map(item_off, "item_off"), mem.map(index, "index")
-    a_slots, a_status = mem.map(slots, "slots"), mem.map(status, "status")
+    a_slots, a_status = mem.map(slots, "slots") - ch0 * stride, mem.map(status, "status")
     a_pf = mem.map(np.array(pf_all, np.int32), "part_first", writable=False)
     tails = bytearray()
     for t in range(T):
         tails += struct.pack("<iiiiiiiiQqQq", first_item[t], first_item[t + 1] - first_item[t], first_part[t] + t, n_parts[t],
-                             first_part[t], 0, 0, 0, a_dsts[t], dst_bytes_per_task[t], a_dsts[t], dst_bytes_per_task[t])
+                             first_part[t], 0, 0, 0, a_dsts[t], dst_bytes_per_task[t], a_dsts[t] - k_dst, dst_bytes_per_task[t] + k_dst)
     a_tails = mem.map(np.frombuffer(tails, dtype=np.uint8), "tails", writable=False)
     a_items = _compress(mem, a_src, items, n_items, a_slots, stride, a_size, windows) if n_items else 0
     prog, entry, objs = _prog("assemble.hip", "scan_items_batch_kernel")
     emu.launch(prog, entry, mem, struct.pack("<QiiQQQQ", a_tails, T, 0, a_size, a_off, a_pf, a_index), T, 0, objects=objs)
+    item_off += k_dst
     if n_items:
         prog, entry, objs = _prog("assemble.hip", "gather_items_batch_kernel")
         emu.launch(prog, entry, mem, struct.pack("<QiiQQQqQQQ", a_tails, T, n_items, a_src, a_items, a_slots, stride, a_size, a_off,
@@ -150,19 +165,21 @@ def compress_map_outputs_batch(tasks, block, dst_bytes_per_task, windows=True):
     return res
 
 
-def compress_fragments(frags, windows=True):
-    """single fragments (<= 64 KiB each) as kItemSnappyChunk items in 64 KiB slots: -> list of raw snappy blocks"""
+def compress_fragments(frags, windows=True, far=None, cross=None):
+    """single fragments (<= 64 KiB each) as kItemSnappyChunk items in 64 KiB slots: -> list of raw snappy blocks
+    (far = {"src": K, "slots": K} / cross: as compress_map_output)"""
     stride = slot_stride(FRAGMENT)
+    k_src, ch0, _ = _far(far, stride)
     items = bytearray()
-    off = 0
+    off = k_src
     for k, c in enumerate(frags):
-        items += struct.pack("<qiiii", off, len(c), K_CHUNK, k, 0)
+        items += struct.pack("<qiiii", off, len(c), K_CHUNK, ch0 + k, 0)
         off += len(c)
-    mem = emu.Memory()
-    a_src = mem.map(np.concatenate([np.asarray(c, np.uint8) for c in frags]), "src", writable=False)
+    mem = emu.Memory(cross)
+    a_src = mem.map(np.concatenate([np.asarray(c, np.uint8) for c in frags]), "src", writable=False) - k_src
     slots = np.zeros(len(frags) * stride, np.uint8)
     size = np.zeros(len(frags), np.uint32)
-    a_slots, a_size = mem.map(slots, "slots"), mem.map(size, "item_size")
+    a_slots, a_size = mem.map(slots, "slots") - ch0 * stride, mem.map(size, "item_size")
     _compress(mem, a_src, items, len(frags), a_slots, stride, a_size, windows)
     out = []
     for k in range(len(frags)):

@@ -33,11 +33,12 @@ def program():
     return _PROG
 
 
-def decode_partitions(parts, profile=None):
+def decode_partitions(parts, profile=None, far=0, cross=None):
     """parts: list of (compressed partition bytes = concatenated frames, decoded size).  Returns (list of decoded bytes or
-    None, list of rc, waves of pass 2)."""
+    None, list of rc, waves of pass 2).  far = K: pass 2 gets `lit - K` and every ZPart.lit_off + K (the partitions' source and
+    destination are absolute pointers); cross = {"comp" / "dst" / "lit": byte}: gfx950_emu.Memory(cross)."""
     prog, entry, text, lds = program()
-    mem = emu.Memory()
+    mem = emu.Memory(cross)
     comp = np.frombuffer(b"".join(p for p, _ in parts) or b"\0", dtype=np.uint8).copy()
     a_comp = mem.map(comp, "comp", writable=False)
     total = sum(n for _, n in parts)
@@ -71,13 +72,13 @@ def decode_partitions(parts, profile=None):
     lit_offs, lit_strides, lit_total = [], [], 0
     live = [rc == 0 and tot <= parts[k][1] for k, (tot, need, rc, _) in enumerate(res1)]
     for k, (tot, need, rc, _) in enumerate(res1):
-        lit_offs.append(lit_total)
+        lit_offs.append(lit_total + far)
         lit_strides.append((need + 64 + 15) & ~15)  # two literal buffers per partition: block k of the literal wavefront -> k & 1
         if live[k]:
             lit_total += 2 * lit_strides[k]
     sizes_ok = [rc == 0 and tot == parts[k][1] for k, (tot, need, rc, _) in enumerate(res1)]
     lit = np.zeros(lit_total + 64, dtype=np.uint8)
-    a_lit = mem.map(lit, "lit")
+    a_lit = mem.map(lit, "lit") - far
     zp2 = zparts(lit_offs, live, [res1[k][0] if live[k] else 0 for k in range(n)], lit_strides)
     a_parts2 = mem.map(zp2, "parts2", writable=False)
     kernarg = struct.pack("<QiiQQ", a_parts2, n, 1, a_lit, a_res)
