@@ -3,14 +3,13 @@
 frames as Spark's ZStdCompressionCodec produces them, other levels, one-shot frames with a content size, checksummed,
 concatenated and skippable frames — must decode to the source, the size pass must agree, and mutated streams must be
 rejected or decoded exactly like libzstd decodes them (never crash, never write past the destination)."""
-import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import corpus
+import zstd_model_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -19,56 +18,17 @@ ROOT = os.path.dirname(HERE)
 # the decoder as it ships (round 4: the one-window sequence read, ex -DZS_SEQ_FASTBITS, is the only build)
 @pytest.fixture(scope="module", params=[""], ids=["shipped"])
 def model(request):
-    src = os.path.join(HERE, "model", "zstd_decode_model.cpp")
-    so = os.path.join(HERE, "model", "zstd_decode_model%s.so" % ("_" + request.param[3:].lower() if request.param else ""))
-    core = os.path.join(ROOT, "spark-s3-shuffle_amd", "csrc", "zstd_decode_core.h")
-    if not os.path.exists(so) or max(os.path.getmtime(src), os.path.getmtime(core)) > os.path.getmtime(so):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", *([request.param] if request.param else []),
-                        src, "-o", so], check=True)
-    m = ctypes.CDLL(so)
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    m.zs_decoded_size.argtypes = [ctypes.c_void_p, ctypes.c_int64, i64p]
-    m.zs_decode.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, i64p]
-    return m
+    return zstd_model_lib.load(request.param)
 
 
-def _decode(model, comp, cap):
-    comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    total = ctypes.c_int64(-1)
-    rc = model.zs_decoded_size(comp.ctypes.data, comp.size, ctypes.byref(total))
-    if rc != 0:
-        return rc, None
-    size = total.value
-    guard = 64
-    out = np.full(max(cap, 0) + guard, 0xA5, dtype=np.uint8)
-    rc = model.zs_decode(comp.ctypes.data, comp.size, out.ctypes.data, cap, ctypes.byref(total))
-    assert np.all(out[cap:] == 0xA5), "decoder wrote past its destination"
-    if rc != 0:
-        return rc, None
-    assert total.value == size, "size pass and decode pass disagree"
-    return 0, out[:size].copy()
-
-
-def _corpora():
-    from s3shuffle import datagen
-
-    rng = np.random.default_rng(7)
-    yield "terasort", datagen.terasort_map_output(700_000, 1, seed=2)[0]
-    yield "wide", datagen.tpcds_wide_map_output(500_000, 1, seed=3)[0]
-    yield "kvint", datagen.kv_int_map_output(120_000, 1, seed=1)[0]
-    yield "zeros", np.zeros(300_000, np.uint8)
-    yield "random", rng.integers(0, 256, 200_000, dtype=np.uint8)
-    for k in range(corpus.N_KINDS):
-        yield "corpus%d" % k, corpus.chunk_corpus(k, 6000 if k == 6 else 90_000, rng)
-    for n in (0, 1, 2, 3, 7, 63, 64, 255, 256, 257, 1000, 4095):
-        yield "tiny%d" % n, rng.integers(0, 4, n, dtype=np.uint8)
+_decode = zstd_model_lib.decode  # (rc, bytes): guard bytes behind the destination, size pass == decode pass
 
 
 def test_streams_libzstd_writes_decode_to_the_source(model):
     from oracle import zstd_ref as z
 
     assert z.version() >= 10400
-    for name, data in _corpora():
+    for name, data in zstd_model_lib.corpora():
         for level in (1, 3, 9, 19, -5):
             comp = z.compress_stream(data, level)
             rc, out = _decode(model, comp, data.size)
