@@ -73,7 +73,7 @@
 extern "C" {
 #endif
 
-#define S3S_ABI_VERSION 10 /* 2: + segments entry points, page-locked staging, tuning options 6, 7;
+#define S3S_ABI_VERSION 11 /* 2: + segments entry points, page-locked staging, tuning options 6, 7;
                              3: + s3s_compress_map_outputs_batch_device;
                              4: + s3s_decompress_ranges_batch_device; decode variants {3, 4}, LZ4 parses {1, 9, 10};
                              5: + s3s_compress_map_outputs_batch / s3s_decompress_ranges_batch (host buffers),
@@ -85,16 +85,20 @@ extern "C" {
                              9: S3S_OPT_SNAPPY_BLOCK_SIZE up to 32 MiB (map side fragment-parallel), Snappy chunks of any
                                 decoded length up to 32 MiB through the batch decoder;
                              10: + S3S_OPT_LZ4_BLOCK_SIZE_LARGE: LZ4 blocks up to 32 MiB on the map side (chunks of 65 547 bytes
-                                 or more through liblz4's 32-bit-table parse) */
+                                 or more through liblz4's 32-bit-table parse);
+                             11: + S3S_OPT_ZSTD_COMPRESS: S3S_CODEC_ZSTD on the map side (decode-compatible Zstandard frames) */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
        S3S_CODEC_LZF = 4, /* reduce side only (ABI 7): LZFCompressionCodec streams (compress-lzf chunks 'Z' 'V' type | len ...
                              around liblzf blocks, up to 65 535 bytes each) through the batch decoder; compression stays on
                              the JVM - compress-lzf's output is not a function of the partition's bytes */
-       S3S_CODEC_ZSTD = 3 /* reduce side only (s3s_decompress_range*, s3s_decompressed_size): Zstandard frames as
+       S3S_CODEC_ZSTD = 3 /* reduce side (s3s_decompress_range*, s3s_decompressed_size): Zstandard frames as
                              ZStdCompressionCodec / zstd-jni write them, one per non-empty partition; the compress
-                             entry points answer S3S_E_UNSUPPORTED (the codec stays on the JVM) */ };
+                             entry points answer S3S_E_UNSUPPORTED (the codec stays on the JVM) unless
+                             S3S_OPT_ZSTD_COMPRESS is 1 (ABI 11): then they write one frame per non-empty segment that every
+                             Zstandard decoder reads - NOT libzstd's bytes: blocks of 128 KiB without history
+                             across blocks, 8-byte Frame_Content_Size, no content checksum, no dictionary */ };
 /* spark.shuffle.checksum.algorithm (NONE when spark.shuffle.checksum.enabled=false) */
 enum { S3S_CHECKSUM_NONE = 0, S3S_CHECKSUM_ADLER32 = 1, S3S_CHECKSUM_CRC32 = 2,
        S3S_CHECKSUM_CRC32C = 3 /* ABI 8: java.util.zip.CRC32C (Castagnoli), Spark 4's third spark.shuffle.checksum.algorithm */ };
@@ -137,7 +141,7 @@ enum {
   S3S_OPT_LZ4_DECODE_VARIANT = 5, /* tuning, identical output, LZ4 and Snappy: 4 (default) = batch decoder
                                     (one sequence per lane, dependency rounds, sliding LDS output window),
                                     3 = ring decoder (one sequence per step, parse on the vector ALU) */
-  S3S_OPT_LZ4_BLOCK_SIZE_LARGE = 8 /* since ABI 10: the same setting as key 1 with the range 64..33554432 (lz4-java's
+  S3S_OPT_LZ4_BLOCK_SIZE_LARGE = 8, /* since ABI 10: the same setting as key 1 with the range 64..33554432 (lz4-java's
                                     MAX_BLOCK_SIZE; above: S3S_E_UNSUPPORTED, below 64: S3S_E_INVALID).  Chunks of 65 547
                                     bytes or more are parsed as liblz4 parses them (4096 x u32 table, 5-byte hash, distance
                                     test) by the general batch whatever S3S_OPT_LZ4_VARIANT says (the exact windows are
@@ -150,6 +154,13 @@ enum {
                                     reserves a slot of 32 + blockSize bytes for the duration of the call, so a task of P
                                     non-empty partitions holds at least P x blockSize (200 partitions at 32m: 6.4 GiB per
                                     context); a call whose workspace cannot be allocated answers S3S_E_NOMEM */
+  S3S_OPT_ZSTD_COMPRESS = 9      /* since ABI 11: 0 (default) / 1, other values S3S_E_INVALID.  0: every compress entry point and
+                                    s3s_max_compressed_size* answer S3S_CODEC_ZSTD as before ABI 11 (S3S_E_UNSUPPORTED, batch
+                                    entries S3S_STATUS_NOT_RUN; S3S_E_INVALID from the sizing helpers) - callers use that
+                                    answer to keep the JVM codec.  1: the caller's explicit choice of a decode-compatible
+                                    writer: the output is a pure function of the source bytes, the offsets and the options,
+                                    decodes under libzstd / zstd-jni and this library, and is not the byte stream libzstd
+                                    would have written.  LZF compression stays refused */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */

@@ -30,7 +30,8 @@ object S3SCodec {
   val STATUS_NOT_RUN = -100 // per-entry status of a batch call that failed before this entry had a verdict: the call's return code is its error
   val OPT_LZ4_BLOCK_SIZE = 1; val OPT_SNAPPY_BLOCK_SIZE = 2
   val OPT_LZ4_BLOCK_SIZE_LARGE = 8 // ABI 10: key 1's setting with the range 64 .. 32m (key 1 keeps refusing values above 64k)
-  val ABI_VERSION = 10
+  val OPT_ZSTD_COMPRESS = 9 // ABI 11: 1 = the compress entry points take CODEC_ZSTD (decode-compatible frames, not libzstd's bytes); 0 (default) refuses it as before
+  val ABI_VERSION = 11
 
   // ---- native entry points (jni/s3s_jni.c, one line each) -------------------------------------------------------
   @native def abiVersion(): Int

@@ -137,6 +137,14 @@ __device__ __forceinline__ void gather_item_body(
     }
     return;
   }
+  if (kind == kItemZstdHeader) {
+    // 28 B5 2F FD | descriptor 0xC0 (8-byte Frame_Content_Size, no checksum, no dictionary) | window 2^17 | content size LE
+    if (tid < kZstdFrameHeader) {
+      const uint64_t lo = 0x38C0FD2FB528ull;
+      d[tid] = tid < 6 ? (uint8_t)(lo >> (8 * tid)) : (uint8_t)((uint64_t)item.src_off >> (8 * (tid - 6)));
+    }
+    return;
+  }
   if (kind == kItemSnappyChunkHead) {
     // a Snappy chunk above one fragment: i32 BE compressed length | varint32(len).  The fragments follow this item, so the
     // raw block is the preamble plus what the scan placed between the first fragment's start and the last one's end.
@@ -154,6 +162,15 @@ __device__ __forceinline__ void gather_item_body(
   const uint8_t* slot = slots + (size_t)item.chunk * (size_t)slot_stride;
   if (kind == kItemSnappyFrag) {  // a fragment's elements, behind the head item (and the fragments in front of it)
     copy_bytes(d, slot + kSlotHeader, n, tid);
+    return;
+  }
+  if (kind == kItemZstdBlock) {  // 3-byte block header, then the content (a Raw_Block's content is the source)
+    if (sz & kRawFlag) {
+      copy_bytes(d, slot + (kSlotHeader - 3), 3, tid);
+      copy_bytes(d + 3, src + item.src_off, n - 3, tid);
+    } else {
+      copy_bytes(d, slot + (kSlotHeader - 3), n, tid);
+    }
     return;
   }
   if (kind == kItemLz4Chunk || kind == kItemLz4ChunkU32) {

@@ -27,6 +27,7 @@ enum BufId {
   B_WORK,  // block counter of the persistent codec grid
   B_PARTIAL2,  // checksum partials of folded segment groups (ranges of more than kChecksumFoldFrom segments)
   B_ZSCRATCH, B_ZPIECES,  // zstd single pass: decoded partitions at guessed capacities, and the compaction's piece list
+  B_ZENC,  // zstd map side: sequences + literals of the blocks in flight, one piece per resident workgroup
   B_TAILS,  // batched calls: one TaskTail per map task / fetched range (s3s_internal.h)
   B_COUNT
 };
@@ -52,6 +53,7 @@ struct s3s_ctx {
   hipEvent_t ev_auto[2] = {nullptr, nullptr};
   int lz4_decode_variant = 4;  // 4 = batch decoder (lz4_decode_batch.hip), 3 = ring decoder on the vector ALU
   int snappy_variant = 1;
+  int zstd_compress = 0;  // S3S_OPT_ZSTD_COMPRESS: the compress entry points take S3S_CODEC_ZSTD (off: S3S_E_UNSUPPORTED, as before ABI 11)
   s3s::DevBuf buf[s3s::B_COUNT];
   int cu_count = 256;  // compute units of the device (persistent grids: resident wavefronts per CU x this)
   void* h_stage = nullptr;  // pinned
@@ -197,6 +199,7 @@ inline int64_t effective_block(const s3s_ctx* ctx, int codec) {
     const int64_t b = ctx ? ctx->snappy_block : 32768;
     return b < 1024 ? 1024 : b;  // snappy-java: Math.max(MIN_BLOCK_SIZE, blockSize)
   }
+  if (codec == S3S_CODEC_ZSTD) return kZstdBlock;
   return 0;
 }
 
@@ -213,6 +216,8 @@ inline int64_t max_partition_size(int codec, int64_t bs, int64_t u) {
       const int64_t full = u / bs, rem = u % bs;
       return kSnappyStreamHeader + full * (4 + snappy_max_len(bs)) + (rem ? 4 + snappy_max_len(rem) : 0);
     }
+    case S3S_CODEC_ZSTD:  // frame header + every block Raw
+      return kZstdFrameHeader + u + 3 * ((u + bs - 1) / bs);
   }
   return -1;
 }

@@ -45,8 +45,14 @@ enum : int32_t {
   // an LZ4Block data frame whose chunk is kLz4U32From bytes or longer (ABI 10): the same frame, slot and item_size as
   // kItemLz4Chunk, parsed by the byU32 kernel.  A kind of its own, so that the kernels of the <= 64 KiB path pass it by
   // without a length test of their own.
-  kItemLz4ChunkU32 = 6
+  kItemLz4ChunkU32 = 6,
+  // Zstandard map side (ABI 11, zstd_compress.hip): one frame per non-empty segment
+  kItemZstdHeader = 7,   // the 14-byte frame header; src_off holds the segment's length (Frame_Content_Size)
+  kItemZstdBlock = 8     // one block of at most kZstdBlock bytes: 3-byte header right-aligned in the slot header, content from
+                         // +32; kind bit 8 = Last_Block; item_size bit 31 = Raw_Block (content copied from the source)
 };
+constexpr int kZstdBlock = 1 << 17;       // Block_Maximum_Size of the frames the map side writes (= s3s_zstd_enc::kBlock)
+constexpr int kZstdFrameHeader = 14;      // magic | descriptor | window | 8-byte content size (= s3s_zstd_enc::kFrameHeader)
 
 // bytes of snappy's varint32 preamble of a block of n bytes
 __host__ __device__ constexpr int snappy_varint_len(int64_t n) {
@@ -81,6 +87,11 @@ bool snappy_compress_available();
 void launch_snappy_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                             uint8_t* d_slots, int64_t slot_stride, uint32_t* d_item_size,
                             int variant, hipStream_t st);  // variant 0: batch only, 1: exact windows first
+// Zstandard: every kItemZstdBlock item into its slot (and its item_size), kItemZstdHeader items get their constant size.
+//   d_scratch: grid x zstd_compress_scratch_stride() bytes (sequences and literals of the block a workgroup is working on)
+int64_t zstd_compress_scratch_stride();
+void launch_zstd_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items, uint8_t* d_slots, int64_t slot_stride,
+                          uint32_t* d_item_size, uint8_t* d_scratch, int32_t grid, hipStream_t st);
 // exclusive scan of item sizes + partition index extraction
 void launch_scan_items(const Item* d_items, const uint32_t* d_item_size, int32_t n_items,
                        int64_t* d_item_off, const int32_t* d_part_first, int32_t n_parts,
