@@ -86,13 +86,20 @@ extern "C" {
                                 decoded length up to 32 MiB through the batch decoder;
                              10: + S3S_OPT_LZ4_BLOCK_SIZE_LARGE: LZ4 blocks up to 32 MiB on the map side (chunks of 65 547 bytes
                                  or more through liblz4's 32-bit-table parse);
-                             11: + S3S_OPT_ZSTD_COMPRESS: S3S_CODEC_ZSTD on the map side (decode-compatible Zstandard frames) */
+                             11: + S3S_OPT_ZSTD_COMPRESS: S3S_CODEC_ZSTD on the map side (decode-compatible Zstandard frames);
+                                 still 11: + S3S_OPT_LZF_COMPRESS (key 10): S3S_CODEC_LZF on the map side.  The key is additive and
+                                 the version did not move: a library without it answers S3S_E_INVALID to
+                                 s3s_set_option(ctx, 10, 1), and that answer is how callers detect support */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
-       S3S_CODEC_LZF = 4, /* reduce side only (ABI 7): LZFCompressionCodec streams (compress-lzf chunks 'Z' 'V' type | len ...
-                             around liblzf blocks, up to 65 535 bytes each) through the batch decoder; compression stays on
-                             the JVM - compress-lzf's output is not a function of the partition's bytes */
+       S3S_CODEC_LZF = 4, /* reduce side (ABI 7): LZFCompressionCodec streams (compress-lzf chunks 'Z' 'V' type | len ...
+                             around liblzf blocks, up to 65 535 bytes each) through the batch decoder.  compress-lzf's output
+                             is not a function of the partition's bytes, so the compress entry points answer
+                             S3S_E_UNSUPPORTED unless S3S_OPT_LZF_COMPRESS is 1: then they write, per non-empty segment, an
+                             LZFOutputStream-shaped stream that every LZF decoder reads - NOT compress-lzf's bytes
+                             (DESIGN.md 6g): chunks of 65 535 source bytes without history across chunks, a chunk whose block
+                             is not two bytes shorter stored */
        S3S_CODEC_ZSTD = 3 /* reduce side (s3s_decompress_range*, s3s_decompressed_size): Zstandard frames as
                              ZStdCompressionCodec / zstd-jni write them, one per non-empty partition; the compress
                              entry points answer S3S_E_UNSUPPORTED (the codec stays on the JVM) unless
@@ -154,13 +161,21 @@ enum {
                                     reserves a slot of 32 + blockSize bytes for the duration of the call, so a task of P
                                     non-empty partitions holds at least P x blockSize (200 partitions at 32m: 6.4 GiB per
                                     context); a call whose workspace cannot be allocated answers S3S_E_NOMEM */
-  S3S_OPT_ZSTD_COMPRESS = 9      /* since ABI 11: 0 (default) / 1, other values S3S_E_INVALID.  0: every compress entry point and
+  S3S_OPT_ZSTD_COMPRESS = 9,     /* since ABI 11: 0 (default) / 1, other values S3S_E_INVALID.  0: every compress entry point and
                                     s3s_max_compressed_size* answer S3S_CODEC_ZSTD as before ABI 11 (S3S_E_UNSUPPORTED, batch
                                     entries S3S_STATUS_NOT_RUN; S3S_E_INVALID from the sizing helpers) - callers use that
                                     answer to keep the JVM codec.  1: the caller's explicit choice of a decode-compatible
                                     writer: the output is a pure function of the source bytes, the offsets and the options,
                                     decodes under libzstd / zstd-jni and this library, and is not the byte stream libzstd
-                                    would have written.  LZF compression stays refused */
+                                    would have written */
+  S3S_OPT_LZF_COMPRESS = 10      /* ABI 11, additive (a library without the key answers S3S_E_INVALID to setting it): 0 (default) /
+                                    1, other values S3S_E_INVALID.  0: every compress entry point and s3s_max_compressed_size*
+                                    answer S3S_CODEC_LZF as before (S3S_E_UNSUPPORTED, batch entries S3S_STATUS_NOT_RUN;
+                                    S3S_E_INVALID from the sizing helpers).  1: the caller's explicit choice of a decode-compatible
+                                    writer: per non-empty segment the chunks 'Z' 'V' 1 | clen | ulen | liblzf block or
+                                    'Z' 'V' 0 | len | bytes of LZFOutputStream, a pure function of the source bytes, the offsets
+                                    and the options; compress-lzf's LZFInputStream, liblzf and this library decode it;
+                                    s3s_max_compressed_size* answer ulen + 7 x ceil(ulen / 65535) per segment */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */

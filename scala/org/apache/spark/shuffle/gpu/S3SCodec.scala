@@ -24,13 +24,14 @@ object S3SCodec {
   // ---- constants of include/s3shuffle_codec.h ----------------------------------------------------------------
   val CODEC_NONE = 0; val CODEC_LZ4 = 1; val CODEC_SNAPPY = 2
   val CODEC_ZSTD = 3 // reduce side only (decompressRange*, decompressedSize): S3GpuBlockDecoder takes ranges of many small frames, INTEGRATION.md
-  val CODEC_LZF = 4 // reduce side only: LZFCompressionCodec streams (compress-lzf chunks around liblzf blocks)
+  val CODEC_LZF = 4 // reduce side; map side only with OPT_LZF_COMPRESS: LZFCompressionCodec streams (compress-lzf chunks around liblzf blocks)
   val CHECKSUM_NONE = 0; val CHECKSUM_ADLER32 = 1; val CHECKSUM_CRC32 = 2; val CHECKSUM_CRC32C = 3
   val OK = 0; val E_INVALID = -1; val E_CAPACITY = -2; val E_BAD_FRAME = -3; val E_CHECKSUM = -4; val E_HIP = -5
   val STATUS_NOT_RUN = -100 // per-entry status of a batch call that failed before this entry had a verdict: the call's return code is its error
   val OPT_LZ4_BLOCK_SIZE = 1; val OPT_SNAPPY_BLOCK_SIZE = 2
   val OPT_LZ4_BLOCK_SIZE_LARGE = 8 // ABI 10: key 1's setting with the range 64 .. 32m (key 1 keeps refusing values above 64k)
   val OPT_ZSTD_COMPRESS = 9 // ABI 11: 1 = the compress entry points take CODEC_ZSTD (decode-compatible frames, not libzstd's bytes); 0 (default) refuses it as before
+  val OPT_LZF_COMPRESS = 10 // ABI 11 (additive: an older library answers E_INVALID to setting it): 1 = the compress entry points take CODEC_LZF (decode-compatible streams, not compress-lzf's bytes); 0 (default) refuses it as before
   val ABI_VERSION = 11
 
   // ---- native entry points (jni/s3s_jni.c, one line each) -------------------------------------------------------

@@ -173,6 +173,15 @@ __device__ __forceinline__ void gather_item_body(
     }
     return;
   }
+  if (kind == kItemLzfChunk) {  // 'Z' 'V' type | lengths, then the block (a stored chunk's bytes are the source)
+    if (sz & kRawFlag) {
+      copy_bytes(d, slot + (kSlotHeader - 5), 5, tid);
+      copy_bytes(d + 5, src + item.src_off, n - 5, tid);
+    } else {
+      copy_bytes(d, slot + (kSlotHeader - 7), n, tid);
+    }
+    return;
+  }
   if (kind == kItemLz4Chunk || kind == kItemLz4ChunkU32) {
     if (sz & kRawFlag) {
       copy_bytes(d, slot + (kSlotHeader - kLz4FrameHeader), kLz4FrameHeader, tid);

@@ -164,6 +164,10 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
       if (value != 0 && value != 1) return fail(ctx, S3S_E_INVALID, "zstd compress must be 0 or 1");
       ctx->zstd_compress = (int)value;
       return S3S_OK;
+    case S3S_OPT_LZF_COMPRESS:  // the same switch for S3S_CODEC_LZF
+      if (value != 0 && value != 1) return fail(ctx, S3S_E_INVALID, "lzf compress must be 0 or 1");
+      ctx->lzf_compress = (int)value;
+      return S3S_OK;
     case S3S_OPT_LZ4_DECODE_VARIANT:
       if (value != 3 && value != 4) return fail(ctx, S3S_E_INVALID, "decode variant must be 3 (ring decoder) or 4 (batch decoder)");
       ctx->lz4_decode_variant = (int)value;
@@ -194,6 +198,7 @@ int64_t s3s_get_option(const s3s_ctx* ctx, int key) {
     case S3S_OPT_LZ4_DECODE_VARIANT: return ctx->lz4_decode_variant;
     case S3S_OPT_SNAPPY_VARIANT: return ctx->snappy_variant;
     case S3S_OPT_ZSTD_COMPRESS: return ctx->zstd_compress;
+    case S3S_OPT_LZF_COMPRESS: return ctx->lzf_compress;
   }
   return S3S_E_INVALID;
 }
@@ -208,7 +213,8 @@ double s3s_stage_ms(const s3s_ctx* ctx, int stage) {
 int64_t s3s_max_compressed_size(const s3s_ctx* ctx, int codec, const int64_t* src_offsets,
                                 int32_t n) {
   if (!src_offsets || n < 0) return S3S_E_INVALID;
-  if (codec != S3S_CODEC_NONE && codec != S3S_CODEC_LZ4 && codec != S3S_CODEC_SNAPPY && !(codec == S3S_CODEC_ZSTD && ctx && ctx->zstd_compress))
+  if (codec != S3S_CODEC_NONE && codec != S3S_CODEC_LZ4 && codec != S3S_CODEC_SNAPPY && !(codec == S3S_CODEC_ZSTD && ctx && ctx->zstd_compress) &&
+      !(codec == S3S_CODEC_LZF && ctx && ctx->lzf_compress))
     return S3S_E_INVALID;
   const int64_t bs = effective_block(ctx, codec);
   int64_t total = 0;
@@ -256,9 +262,9 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
   if (pfs[0] != 0 || pfs[n] != ns) return fail(ctx, S3S_E_INVALID, "part_first_seg must start at 0 and end at n_segs");
   for (int32_t p = 0; p < n; p++)
     if (pfs[p + 1] < pfs[p]) return fail(ctx, S3S_E_INVALID, "part_first_seg not monotonic at %d", p);
-  if ((codec == S3S_CODEC_ZSTD && !ctx->zstd_compress) || codec == S3S_CODEC_LZF)
+  if ((codec == S3S_CODEC_ZSTD && !ctx->zstd_compress) || (codec == S3S_CODEC_LZF && !ctx->lzf_compress))
     return fail(ctx, S3S_E_UNSUPPORTED, "%s compression stays on the JVM codec (decode only: s3s_decompress_range*)", codec == S3S_CODEC_LZF ? "lzf" : "zstd");
-  if (codec != S3S_CODEC_NONE && codec != S3S_CODEC_LZ4 && codec != S3S_CODEC_SNAPPY && codec != S3S_CODEC_ZSTD)
+  if (codec != S3S_CODEC_NONE && codec != S3S_CODEC_LZ4 && codec != S3S_CODEC_SNAPPY && codec != S3S_CODEC_ZSTD && codec != S3S_CODEC_LZF)
     return fail(ctx, S3S_E_INVALID, "unknown codec %d", codec);
   if (checksum_algo != S3S_CHECKSUM_NONE && checksum_algo != S3S_CHECKSUM_ADLER32 && checksum_algo != S3S_CHECKSUM_CRC32 &&
       checksum_algo != S3S_CHECKSUM_CRC32C)
@@ -287,7 +293,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
       } else if (u > 0) {
         const int64_t ch = (u + bs - 1) / bs;
         n_chunks64 += ch;
-        n_items64 += ch + 1;  // + LZ4 end frame / Zstandard frame header
+        n_items64 += ch + (codec != S3S_CODEC_LZF);  // + LZ4 end frame / Zstandard frame header; an LZF stream is its chunks
       }
     }
   }
@@ -336,6 +342,10 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
             h_items[it++] = Item{seg_offsets[g] + pos, len, kItemZstdBlock | ((pos + len == u) << 8), ch++, p};
             continue;
           }
+          if (codec == S3S_CODEC_LZF) {
+            h_items[it++] = Item{seg_offsets[g] + pos, len, kItemLzfChunk, ch++, p};
+            continue;
+          }
           h_items[it++] = Item{seg_offsets[g] + pos, len, lz4_chunk_kind(len) | (level << 8), ch++, p};
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
@@ -369,8 +379,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
     if ((rc = ensure(ctx, B_PART_FIRST, pf_bytes))) return rc;
     // a slot holds one chunk's codec output: LZ4 payloads never exceed the chunk (RAW fallback), a raw
     // snappy block can grow to MaxCompressedLength(chunk); a Snappy slot holds at most one 64 KiB fragment
-    const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs)
-                                                          : (int64_t)kSlotHeader + ((bs + 15) & ~int64_t(15));
+    const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
     if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(n_chunks > 0 ? n_chunks : 1)))) return rc;
     if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
     if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * (size_t)(n_items + 1)))) return rc;
@@ -412,6 +421,9 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
       else if (codec == S3S_CODEC_ZSTD)
         launch_zstd_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
                              dev<uint32_t>(ctx, B_ITEM_SIZE) + i0, dev<uint8_t>(ctx, B_ZENC), zstd_grid, ctx->stream);
+      else if (codec == S3S_CODEC_LZF)
+        launch_lzf_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
+                            dev<uint32_t>(ctx, B_ITEM_SIZE) + i0, ctx->stream);
       else
         launch_snappy_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
                                dev<uint32_t>(ctx, B_ITEM_SIZE) + i0, ctx->snappy_variant, ctx->stream);
@@ -533,9 +545,9 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
   // "stamped on entry" (s3shuffle_codec.h): BEFORE the argument checks below, so a caller with zeroed status fields never reads
   // S3S_OK out of a call that was refused (advisor r4)
   BatchVerdict<s3s_map_task> verdict(tasks, n_tasks);
-  if ((codec == S3S_CODEC_ZSTD && !ctx->zstd_compress) || codec == S3S_CODEC_LZF)
+  if ((codec == S3S_CODEC_ZSTD && !ctx->zstd_compress) || (codec == S3S_CODEC_LZF && !ctx->lzf_compress))
     return fail(ctx, S3S_E_UNSUPPORTED, "%s compression stays on the JVM codec (decode only: s3s_decompress_range*)", codec == S3S_CODEC_LZF ? "lzf" : "zstd");
-  if (codec != S3S_CODEC_NONE && codec != S3S_CODEC_LZ4 && codec != S3S_CODEC_SNAPPY && codec != S3S_CODEC_ZSTD)
+  if (codec != S3S_CODEC_NONE && codec != S3S_CODEC_LZ4 && codec != S3S_CODEC_SNAPPY && codec != S3S_CODEC_ZSTD && codec != S3S_CODEC_LZF)
     return fail(ctx, S3S_E_INVALID, "unknown codec %d", codec);
   if (checksum_algo != S3S_CHECKSUM_NONE && checksum_algo != S3S_CHECKSUM_ADLER32 && checksum_algo != S3S_CHECKSUM_CRC32 &&
       checksum_algo != S3S_CHECKSUM_CRC32C)
@@ -572,7 +584,7 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
       } else if (u > 0) {
         const int64_t ch = (u + bs - 1) / bs;
         n_chunks64 += ch;
-        n_items64 += ch + 1;
+        n_items64 += ch + (codec != S3S_CODEC_LZF);
       }
     }
     const int64_t tu = k.num_partitions > 0 ? k.src_offsets[k.num_partitions] - k.src_offsets[0] : 0;
@@ -629,6 +641,10 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
             h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kItemZstdBlock | ((pos + len == u) << 8), ch++, p};
             continue;
           }
+          if (codec == S3S_CODEC_LZF) {
+            h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kItemLzfChunk, ch++, p};
+            continue;
+          }
           h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, lz4_chunk_kind(len) | (level << 8), ch++, p};
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
@@ -643,8 +659,7 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
     first_seg[(size_t)n_tasks] = seg;
   }
   const int32_t total_segs = first_seg[(size_t)n_tasks];
-  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs)
-                                                        : (int64_t)kSlotHeader + ((bs + 15) & ~int64_t(15));
+  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
   if ((rc = ensure(ctx, B_ITEMS, items_bytes + 16))) return rc;
   if ((rc = ensure(ctx, B_PART_FIRST, 4 * np1))) return rc;
   if ((rc = ensure(ctx, B_SEG_START, 4 * np1))) return rc;
@@ -696,6 +711,9 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
   } else if (codec == S3S_CODEC_ZSTD) {
     launch_zstd_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
                          dev<uint8_t>(ctx, B_ZENC), zstd_grid, ctx->stream);
+  } else if (codec == S3S_CODEC_LZF) {
+    launch_lzf_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
+                        ctx->stream);
   } else {
     launch_snappy_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
                            dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->snappy_variant, ctx->stream);

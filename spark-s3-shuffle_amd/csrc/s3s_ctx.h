@@ -54,6 +54,7 @@ struct s3s_ctx {
   int lz4_decode_variant = 4;  // 4 = batch decoder (lz4_decode_batch.hip), 3 = ring decoder on the vector ALU
   int snappy_variant = 1;
   int zstd_compress = 0;  // S3S_OPT_ZSTD_COMPRESS: the compress entry points take S3S_CODEC_ZSTD (off: S3S_E_UNSUPPORTED, as before ABI 11)
+  int lzf_compress = 0;   // S3S_OPT_LZF_COMPRESS: the same switch for S3S_CODEC_LZF
   s3s::DevBuf buf[s3s::B_COUNT];
   int cu_count = 256;  // compute units of the device (persistent grids: resident wavefronts per CU x this)
   void* h_stage = nullptr;  // pinned
@@ -193,6 +194,12 @@ inline int64_t snappy_slot_stride(int64_t bs) {
   return (int64_t)kSlotHeader + ((snappy_max_len(n) + 15) & ~int64_t(15));
 }
 
+// bytes between the slots of one call that is not Snappy's: LZ4 and Zstandard payloads never exceed the chunk (RAW fallback);
+// an LZF block is written in full before the chunk is declared stored
+inline int64_t codec_slot_stride(int codec, int64_t bs) {
+  return (int64_t)kSlotHeader + (codec == S3S_CODEC_LZF ? (int64_t)kLzfSlotPayload : ((bs + 15) & ~int64_t(15)));
+}
+
 inline int64_t effective_block(const s3s_ctx* ctx, int codec) {
   if (codec == S3S_CODEC_LZ4) return ctx ? ctx->lz4_block : 32768;
   if (codec == S3S_CODEC_SNAPPY) {
@@ -200,6 +207,7 @@ inline int64_t effective_block(const s3s_ctx* ctx, int codec) {
     return b < 1024 ? 1024 : b;  // snappy-java: Math.max(MIN_BLOCK_SIZE, blockSize)
   }
   if (codec == S3S_CODEC_ZSTD) return kZstdBlock;
+  if (codec == S3S_CODEC_LZF) return kLzfChunk;
   return 0;
 }
 
@@ -218,6 +226,8 @@ inline int64_t max_partition_size(int codec, int64_t bs, int64_t u) {
     }
     case S3S_CODEC_ZSTD:  // frame header + every block Raw
       return kZstdFrameHeader + u + 3 * ((u + bs - 1) / bs);
+    case S3S_CODEC_LZF:  // 7 bytes per chunk (the header of a compressed chunk; a stored one has 5)
+      return u + 7 * ((u + bs - 1) / bs);
   }
   return -1;
 }

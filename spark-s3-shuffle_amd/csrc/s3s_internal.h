@@ -48,9 +48,15 @@ enum : int32_t {
   kItemLz4ChunkU32 = 6,
   // Zstandard map side (ABI 11, zstd_compress.hip): one frame per non-empty segment
   kItemZstdHeader = 7,   // the 14-byte frame header; src_off holds the segment's length (Frame_Content_Size)
-  kItemZstdBlock = 8     // one block of at most kZstdBlock bytes: 3-byte header right-aligned in the slot header, content from
+  kItemZstdBlock = 8,    // one block of at most kZstdBlock bytes: 3-byte header right-aligned in the slot header, content from
                          // +32; kind bit 8 = Last_Block; item_size bit 31 = Raw_Block (content copied from the source)
+  // LZF map side (S3S_OPT_LZF_COMPRESS, lzf_compress.hip): one chunk of at most kLzfChunk bytes - the 7-byte ('Z' 'V' 1 | clen |
+  // ulen) or 5-byte ('Z' 'V' 0 | len) header right-aligned in the slot header, the liblzf block from +32; item_size bit 31 =
+  // stored chunk (bytes copied from the source)
+  kItemLzfChunk = 9
 };
+constexpr int kLzfChunk = 65535;          // source bytes of an LZFOutputStream chunk (= s3s_lzf_enc::kChunk)
+constexpr int kLzfSlotPayload = (kLzfChunk + kLzfChunk / 32 + 4 + 15) & ~15;  // the largest block the parse writes, rounded up
 constexpr int kZstdBlock = 1 << 17;       // Block_Maximum_Size of the frames the map side writes (= s3s_zstd_enc::kBlock)
 constexpr int kZstdFrameHeader = 14;      // magic | descriptor | window | 8-byte content size (= s3s_zstd_enc::kFrameHeader)
 
@@ -92,6 +98,9 @@ void launch_snappy_compress(const uint8_t* d_src, const Item* d_items, int32_t n
 int64_t zstd_compress_scratch_stride();
 void launch_zstd_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items, uint8_t* d_slots, int64_t slot_stride,
                           uint32_t* d_item_size, uint8_t* d_scratch, int32_t grid, hipStream_t st);
+// LZF: every kItemLzfChunk item into its slot (and its item_size); one wavefront per item
+void launch_lzf_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items, uint8_t* d_slots, int64_t slot_stride,
+                         uint32_t* d_item_size, hipStream_t st);
 // exclusive scan of item sizes + partition index extraction
 void launch_scan_items(const Item* d_items, const uint32_t* d_item_size, int32_t n_items,
                        int64_t* d_item_off, const int32_t* d_part_first, int32_t n_parts,

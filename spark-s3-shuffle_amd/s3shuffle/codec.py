@@ -9,7 +9,7 @@ import numpy as np
 
 CODEC_NONE, CODEC_LZ4, CODEC_SNAPPY = 0, 1, 2
 CODEC_ZSTD = 3  # decode of Zstandard frames; the compress entry points refuse it unless OPT_ZSTD_COMPRESS is 1 (ABI 11)
-CODEC_LZF = 4  # reduce side only: LZFCompressionCodec streams (compress-lzf chunks around liblzf blocks)
+CODEC_LZF = 4  # LZFCompressionCodec streams (compress-lzf chunks around liblzf blocks); compression only with OPT_LZF_COMPRESS = 1
 CHECKSUM_NONE, CHECKSUM_ADLER32, CHECKSUM_CRC32, CHECKSUM_CRC32C = 0, 1, 2, 3
 
 OPT_LZ4_BLOCK_SIZE, OPT_SNAPPY_BLOCK_SIZE, OPT_PROFILE = 1, 2, 3
@@ -21,6 +21,7 @@ OPT_LZ4_VARIANT_USED = 7
 OPT_LZ4_BLOCK_SIZE_LARGE = 8  # ABI 10: spark.io.compression.lz4.blockSize 64 .. 32m (key 1 stops at 64k and keeps doing so)
 
 OPT_ZSTD_COMPRESS = 9  # ABI 11: 1 = write decode-compatible Zstandard frames on the map side (not libzstd's bytes); default 0
+OPT_LZF_COMPRESS = 10  # ABI 11, additive key: 1 = write decode-compatible LZF streams on the map side (not compress-lzf's bytes); default 0
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
 STATUS_NOT_RUN = -100  # per-entry status of a batch call that failed as a call before this entry had a verdict (ABI 6)
