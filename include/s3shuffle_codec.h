@@ -89,7 +89,11 @@ extern "C" {
                              11: + S3S_OPT_ZSTD_COMPRESS: S3S_CODEC_ZSTD on the map side (decode-compatible Zstandard frames);
                                  still 11: + S3S_OPT_LZF_COMPRESS (key 10): S3S_CODEC_LZF on the map side.  The key is additive and
                                  the version did not move: a library without it answers S3S_E_INVALID to
-                                 s3s_set_option(ctx, 10, 1), and that answer is how callers detect support */
+                                 s3s_set_option(ctx, 10, 1), and that answer is how callers detect support;
+                                 still 11: + Spark IO encryption (AES/CTR/NoPadding) as a layer on both sides of the codec:
+                                 s3s_set_io_encryption, s3s_set_stream_ivs and the read-only key 11.  Additive again: a caller
+                                 detects support by the symbols, or by s3s_get_option(ctx, 11) answering 0 instead of
+                                 S3S_E_INVALID */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
@@ -168,7 +172,7 @@ enum {
                                     writer: the output is a pure function of the source bytes, the offsets and the options,
                                     decodes under libzstd / zstd-jni and this library, and is not the byte stream libzstd
                                     would have written */
-  S3S_OPT_LZF_COMPRESS = 10      /* ABI 11, additive (a library without the key answers S3S_E_INVALID to setting it): 0 (default) /
+  S3S_OPT_LZF_COMPRESS = 10,     /* ABI 11, additive (a library without the key answers S3S_E_INVALID to setting it): 0 (default) /
                                     1, other values S3S_E_INVALID.  0: every compress entry point and s3s_max_compressed_size*
                                     answer S3S_CODEC_LZF as before (S3S_E_UNSUPPORTED, batch entries S3S_STATUS_NOT_RUN;
                                     S3S_E_INVALID from the sizing helpers).  1: the caller's explicit choice of a decode-compatible
@@ -176,6 +180,9 @@ enum {
                                     'Z' 'V' 0 | len | bytes of LZFOutputStream, a pure function of the source bytes, the offsets
                                     and the options; compress-lzf's LZFInputStream, liblzf and this library decode it;
                                     s3s_max_compressed_size* answer ulen + 7 x ceil(ulen / 65535) per segment */
+  S3S_OPT_IO_ENCRYPTION_KEY_BITS = 11 /* ABI 11, additive, READ-ONLY: 0 (the layer is off), 128, 192 or 256 - the key that
+                                    s3s_set_io_encryption holds.  s3s_set_option on it answers S3S_E_INVALID; a library without
+                                    the layer answers S3S_E_INVALID to s3s_get_option too, which is how callers detect it */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */
@@ -203,6 +210,36 @@ void s3s_destroy(s3s_ctx* ctx);
 const char* s3s_last_error(const s3s_ctx* ctx);
 int s3s_set_option(s3s_ctx* ctx, int key, int64_t value);
 int64_t s3s_get_option(const s3s_ctx* ctx, int key);
+/* ---- Spark IO encryption (spark.io.encryption.enabled): AES/CTR/NoPadding as a layer on both sides of the codec --------
+ * The format is CryptoStreamUtils.createCryptoOutputStream restated (parity with a JVM unpinned): a non-empty
+ * partition is stored as  IV (16 bytes) | AES-CTR_K(codec bytes of the partition)  with key stream block j =
+ * AES_K((IV as a 128-bit big-endian integer + j) mod 2^128); an empty partition stays 0 bytes.  A partition is ONE encrypted
+ * stream whatever its segments were (with encryption on Spark merges spills through the slow path): in the segments forms
+ * the IV belongs to the partition and the codec streams of its segments are concatenated under one key stream.  Index and
+ * checksums cover IV plus cipher text.
+ *
+ * s3s_set_io_encryption: key_bytes 16, 24 or 32 (spark.io.encryption.keySizeBits) switches the layer on for every later call
+ * of this context, on both sides; key == NULL or key_bytes == 0 switches it off and wipes the key; any other length is
+ * S3S_E_INVALID and changes nothing.  The key is copied (as round keys, host memory of the context only - it reaches the
+ * kernels as launch arguments and is never stored in device memory), wiped in s3s_destroy too, and no key byte ever appears
+ * in s3s_last_error.  With the layer off every path, plan and byte is what it was without these entry points.
+ *
+ * Map side: every compress entry point, every codec.  s3s_max_compressed_size* with a context that has the layer on add
+ * 16 per non-empty partition (the segments form, which does not know the partitions: per non-empty segment, an upper bound).
+ * Reduce side: part_offsets index the encrypted bytes; checksums are verified over the bytes as stored, first; then each
+ * non-empty partition's IV is read and the cipher text decrypted into the workspace, where discovery and the decoders run
+ * unchanged.  A non-empty partition of 1..15 bytes is S3S_E_BAD_FRAME; one of exactly 16 bytes is an empty stream.
+ * s3s_decompressed_size with the layer on treats comp as ONE partition, IV first (it decrypts the partition on the host):
+ * callers size a range of several partitions partition by partition.  The batched forms of both sides give the same results
+ * as without the layer but run their tasks / ranges one after the other while it is on. */
+int s3s_set_io_encryption(s3s_ctx* ctx, const uint8_t* key, int32_t key_bytes);
+/* One IV per PARTITION of the NEXT compress call on this context: a host array of 16 * n_ivs bytes, task by task, then
+ * partition by partition; an empty partition has an entry that is not used.  That call consumes the array, whether it
+ * succeeds or fails.  A compress call with the layer on and a count other than its own number of partitions answers
+ * S3S_E_INVALID before anything is allocated or launched (batch entries: S3S_STATUS_NOT_RUN).  The library never invents an
+ * IV (a JVM shim fills them from SecureRandom, as CryptoStreamUtils.createInitializationVector does): the output stays a
+ * pure function of source, offsets, options, key and IVs.  Never reusing an IV under one key is the caller's duty. */
+int s3s_set_stream_ivs(s3s_ctx* ctx, const uint8_t* ivs, int64_t n_ivs);
 /* The HIP stream (hipStream_t) the context launches on, for callers that time with events. */
 void* s3s_stream(const s3s_ctx* ctx);
 double s3s_stage_ms(const s3s_ctx* ctx, int stage);

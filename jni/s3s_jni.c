@@ -57,6 +57,22 @@ JNIEXPORT jstring JNICALL FN(lastError)(JNIEnv* e, jclass c, jlong h) {
   return (*e)->NewStringUTF(e, s3s_last_error(CTX(h)));
 }
 
+/* ---- Spark IO encryption: key and per-partition IVs (direct ByteBuffers: keyBytes / 16 * nIvs bytes are read) -------
+ * The two library symbols are WEAK here: a libs3shuffle_codec.so from before the layer still loads, and the natives then
+ * answer S3S_E_UNSUPPORTED - the answer S3SCodec uses to keep the JVM path under spark.io.encryption.enabled. */
+extern int s3s_set_io_encryption(s3s_ctx* ctx, const uint8_t* key, int32_t key_bytes) __attribute__((weak));
+extern int s3s_set_stream_ivs(s3s_ctx* ctx, const uint8_t* ivs, int64_t n_ivs) __attribute__((weak));
+JNIEXPORT jint JNICALL FN(setIoEncryption)(JNIEnv* e, jclass c, jlong h, jobject key, jint keyBytes) {
+  (void)c;
+  if (!s3s_set_io_encryption) return S3S_E_UNSUPPORTED;
+  return s3s_set_io_encryption(CTX(h), addr(e, key), keyBytes);
+}
+JNIEXPORT jint JNICALL FN(setStreamIvs)(JNIEnv* e, jclass c, jlong h, jobject ivs, jlong nIvs) {
+  (void)c;
+  if (!s3s_set_stream_ivs) return S3S_E_UNSUPPORTED;
+  return s3s_set_stream_ivs(CTX(h), addr(e, ivs), nIvs);
+}
+
 /* ---- page-locked staging: the shim's direct ByteBuffers come from here, never from allocateDirect ------------ */
 JNIEXPORT jobject JNICALL FN(hostAlloc)(JNIEnv* e, jclass c, jlong bytes) {
   (void)c;

@@ -32,6 +32,8 @@ object S3SCodec {
   val OPT_LZ4_BLOCK_SIZE_LARGE = 8 // ABI 10: key 1's setting with the range 64 .. 32m (key 1 keeps refusing values above 64k)
   val OPT_ZSTD_COMPRESS = 9 // ABI 11: 1 = the compress entry points take CODEC_ZSTD (decode-compatible frames, not libzstd's bytes); 0 (default) refuses it as before
   val OPT_LZF_COMPRESS = 10 // ABI 11 (additive: an older library answers E_INVALID to setting it): 1 = the compress entry points take CODEC_LZF (decode-compatible streams, not compress-lzf's bytes); 0 (default) refuses it as before
+  val OPT_IO_ENCRYPTION_KEY_BITS = 11 // ABI 11 (additive, read-only): 0 / 128 / 192 / 256 - the key setIoEncryption holds; an older library answers E_INVALID to getOption
+  val E_UNSUPPORTED = -6
   val ABI_VERSION = 11
 
   // ---- native entry points (jni/s3s_jni.c, one line each) -------------------------------------------------------
@@ -42,6 +44,12 @@ object S3SCodec {
   @native def setOption(handle: Long, key: Int, value: Long): Int
   @native def getOption(handle: Long, key: Int): Long
   @native def lastError(handle: Long): String
+  // Spark IO encryption (spark.io.encryption.enabled, AES/CTR/NoPadding) as a layer on both sides of the codec: `key` is a direct
+  // buffer of keyBytes = 16 / 24 / 32 bytes (SparkEnv.get.securityManager.getIOEncryptionKey()), null switches the layer off;
+  // `ivs` a direct buffer of 16 * nIvs bytes, one IV per partition of the NEXT compress call, filled from SecureRandom as
+  // CryptoStreamUtils.createInitializationVector does - the library never invents one.  E_UNSUPPORTED: a library from before the layer.
+  @native def setIoEncryption(handle: Long, key: ByteBuffer, keyBytes: Int): Int
+  @native def setStreamIvs(handle: Long, ivs: ByteBuffer, nIvs: Long): Int
   @native def hostAlloc(bytes: Long): ByteBuffer
   @native def hostFree(buffer: ByteBuffer): Unit
   @native def maxCompressedSize(handle: Long, codec: Int, srcOffsets: Array[Long], n: Int): Long

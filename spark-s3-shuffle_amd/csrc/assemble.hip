@@ -159,6 +159,7 @@ __device__ __forceinline__ void gather_item_body(
     }
     return;
   }
+  if (kind == kItemIv) return;  // 16 bytes the AES-CTR pass fills (aes_ctr.hip)
   const uint8_t* slot = slots + (size_t)item.chunk * (size_t)slot_stride;
   if (kind == kItemSnappyFrag) {  // a fragment's elements, behind the head item (and the fragments in front of it)
     copy_bytes(d, slot + kSlotHeader, n, tid);

@@ -7,6 +7,8 @@
 // raises "Invalid checksum detected" — reported here as S3S_E_CHECKSUM with the partition
 // number — and a corrupted frame raises "Stream is corrupted" (S3S_E_BAD_FRAME).
 #include "s3s_ctx.h"
+#define S3S_AES_DEVICE
+#include "aes_ctr_core.h"  // (host use only: s3s_decompressed_size decrypts the partition it walks)
 
 using namespace s3s;
 
@@ -88,6 +90,54 @@ int snappy_decoded_size_host(const uint8_t* c, int64_t n, int64_t* out) {
   return S3S_OK;
 }
 
+// Spark IO encryption on the reduce side: the checksums of the bytes AS STORED first, then every non-empty partition's IV is
+// read and its cipher text decrypted into the workspace (IVs dropped, offsets adjusted); discovery and the decoders run on
+// that buffer as they are, through the same entry point with the layer suspended.
+int decompress_encrypted_range(s3s_ctx* ctx, int codec, int checksum_algo, const uint8_t* d_comp, int64_t comp_len,
+                               const int64_t* part_offsets, const int64_t* ref_checksums, int32_t n, uint8_t* d_dst,
+                               int64_t dst_capacity, int64_t* out_len, int32_t* out_bad_partition) {
+  int rc;
+  if (checksum_algo != S3S_CHECKSUM_NONE && n > 0) {
+    std::vector<int64_t> sums((size_t)n);
+    if ((rc = s3s_checksum_ranges_device(ctx, checksum_algo, d_comp, part_offsets, n, sums.data()))) return rc;
+    for (int32_t p = 0; p < n; p++)
+      if (sums[(size_t)p] != ref_checksums[p]) {
+        if (out_bad_partition) *out_bad_partition = p;
+        return fail(ctx, S3S_E_CHECKSUM, "Invalid checksum detected for partition %d of the range", p);
+      }
+  }
+  if (comp_len > aes_ctr_max_bytes()) return fail(ctx, S3S_E_UNSUPPORTED, "range too large for one encrypted call");
+  std::vector<int64_t> plain((size_t)n + 1, 0);
+  for (int32_t p = 0; p < n; p++) {
+    const int64_t len = part_offsets[p + 1] - part_offsets[p];
+    if (len > 0 && len < 16)
+      return fail(ctx, S3S_E_BAD_FRAME, "Stream is corrupted (partition %d: %lld stored bytes, shorter than the IV)", p, (long long)len);
+    plain[(size_t)p + 1] = plain[(size_t)p] + (len > 0 ? len - 16 : 0);
+  }
+  const int64_t plain_len = plain[(size_t)n];
+  if (n > 0 && comp_len > 0) {
+    const size_t off_bytes = sizeof(int64_t) * (size_t)(n + 1);
+    if ((rc = ensure_stage(ctx, 2 * off_bytes))) return rc;
+    if ((rc = ensure(ctx, B_CRYPT, (size_t)plain_len + 64))) return rc;
+    if ((rc = ensure(ctx, B_CRYPT_OFF, 2 * off_bytes))) return rc;
+    int64_t* h = static_cast<int64_t*>(ctx->h_stage);
+    memcpy(h, part_offsets, off_bytes);
+    memcpy(h + (n + 1), plain.data(), off_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_CRYPT_OFF].p, h, 2 * off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_aes_ctr(kCtrDecrypt, ctx->enc_keys, ctx->enc_rounds, d_comp, dev<uint8_t>(ctx, B_CRYPT), dev<int64_t>(ctx, B_CRYPT_OFF),
+                   dev<int64_t>(ctx, B_CRYPT_OFF) + (n + 1), nullptr, n, comp_len, comp_len, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the wrapped call reuses the pinned staging area)
+  }
+  struct Suspend {
+    s3s_ctx* c;
+    ~Suspend() { c->enc_suspended = false; }
+  } suspend{ctx};
+  ctx->enc_suspended = true;
+  return s3s_decompress_range_device(ctx, codec, S3S_CHECKSUM_NONE, plain_len > 0 ? dev<uint8_t>(ctx, B_CRYPT) : nullptr, plain_len,
+                                     plain.data(), nullptr, n, d_dst, dst_capacity, out_len, out_bad_partition);
+}
+
 }  // namespace
 
 extern "C" {
@@ -98,6 +148,22 @@ int s3s_decompressed_size(s3s_ctx* ctx, int codec, const uint8_t* comp, int64_t 
   ctx->err[0] = 0;
   if (comp_len < 0 || (comp_len > 0 && !comp) || !out_len) return fail(ctx, S3S_E_INVALID, "null/invalid argument");
   int rc;
+  if (enc_on(ctx)) {
+    // IO encryption: comp is ONE stored partition, IV first (a range of several partitions is sized partition by partition).
+    // The partition is decrypted on the host and walked as it would be without the layer
+    *out_len = 0;
+    if (comp_len == 0) return S3S_OK;
+    if (comp_len < 16) return fail(ctx, S3S_E_BAD_FRAME, "Stream is corrupted (%lld stored bytes, shorter than the IV)", (long long)comp_len);
+    std::vector<uint8_t> plain((size_t)(comp_len - 16));
+    s3s_aes::keystream(ctx->enc_keys.rk, ctx->enc_rounds, comp, 0, plain.data(), (uint64_t)plain.size(), s3s_aes::TableSbox{});
+    for (size_t i = 0; i < plain.size(); i++) plain[i] ^= comp[16 + i];
+    struct Suspend {
+      s3s_ctx* c;
+      ~Suspend() { c->enc_suspended = false; }
+    } suspend{ctx};
+    ctx->enc_suspended = true;
+    return s3s_decompressed_size(ctx, codec, plain.data(), (int64_t)plain.size(), out_len);
+  }
   switch (codec) {
     case S3S_CODEC_NONE:
       *out_len = comp_len;
@@ -160,6 +226,9 @@ int s3s_decompress_range_device(s3s_ctx* ctx, int codec, int checksum_algo, cons
   if ((comp_len > 0 && !d_comp) || (dst_capacity > 0 && !d_dst)) return fail(ctx, S3S_E_INVALID, "null data pointer");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (auto& v : ctx->stage_ms) v = 0;
+  if (enc_on(ctx))
+    return decompress_encrypted_range(ctx, codec, checksum_algo, d_comp, comp_len, part_offsets, ref_checksums, nparts, d_dst,
+                                      dst_capacity, out_len, out_bad_partition);
   if (codec == S3S_CODEC_ZSTD) {  // one wavefront per partition, two passes (zstd_decompress.hip)
     s3s_fetch_range k{};
     k.d_comp = d_comp;
@@ -390,8 +459,9 @@ int s3s_decompress_range(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
   int64_t need = dst_capacity;
   {
     int64_t decoded = 0;
-    if (codec == S3S_CODEC_ZSTD)
-      ;  // (its size pass runs on the device inside the call below; the caller sized dst with s3s_decompressed_size)
+    if (codec == S3S_CODEC_ZSTD || enc_on(ctx))
+      ;  // (its size pass runs on the device inside the call below; the caller sized dst with s3s_decompressed_size.  Under IO
+         // encryption the frame headers are cipher text: the device path reports the decoded size)
     else if (codec != S3S_CODEC_NONE && s3s_decompressed_size(ctx, codec, comp, comp_len, &decoded) == S3S_OK && decoded < need)
       need = decoded;
     else if (codec == S3S_CODEC_NONE && comp_len < need)
@@ -460,7 +530,7 @@ extern "C" int s3s_decompress_ranges_batch_device(s3s_ctx* ctx, int codec, int c
     return S3S_OK;
   };
   if (n_ranges == 0) return S3S_OK;
-  if (codec == S3S_CODEC_NONE || n_ranges == 1) {  // nothing to batch
+  if (codec == S3S_CODEC_NONE || n_ranges == 1 || enc_on(ctx)) {  // nothing to batch; under IO encryption the ranges run one by one
     for (int32_t r = 0; r < n_ranges; r++) single(R[r]);
     return verdict.finish(first_error());
   }

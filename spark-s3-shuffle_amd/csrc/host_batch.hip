@@ -129,6 +129,7 @@ extern "C" {
 int s3s_compress_map_outputs_batch(s3s_ctx* ctx, int codec, int checksum_algo, s3s_map_task* tasks, int32_t n_tasks) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
+  const IvScope iv_scope(ctx);  // IO encryption: this call owns the IVs of s3s_set_stream_ivs, its groups get their slices below
   if (n_tasks < 0 || (n_tasks > 0 && !tasks)) return fail(ctx, S3S_E_INVALID, "null task array or negative count");
   if (n_tasks == 0) return S3S_OK;
   BatchVerdict<s3s_map_task> verdict(tasks, n_tasks);  // (a call-level failure leaves NOT_RUN marks: the return code is theirs)
@@ -146,6 +147,10 @@ int s3s_compress_map_outputs_batch(s3s_ctx* ctx, int codec, int checksum_algo, s
     cap[(size_t)t] = k.dst_capacity < bound ? k.dst_capacity : bound;
     if ((u[(size_t)t] > 0 && !k.d_src) || (k.dst_capacity > 0 && !k.d_dst)) return fail(ctx, S3S_E_INVALID, "task %d: null host buffer", t);
   }
+  std::vector<int64_t> part0((size_t)n_tasks + 1, 0);  // partitions in front of every task: its place in the IV array
+  for (int32_t t = 0; t < n_tasks; t++) part0[(size_t)t + 1] = part0[(size_t)t] + tasks[t].num_partitions;
+  if (int iv_rc = enc_check_ivs(ctx, part0[(size_t)n_tasks])) return iv_rc;  // before anything is allocated or launched
+  const uint8_t* const call_ivs = ctx->iv_cur;
   if (n_tasks == 1) {  // nothing to pipeline across tasks: the single-task path overlaps its own upload in chunks
     s3s_map_task& k = tasks[0];
     k.status = s3s_compress_map_output(ctx, codec, checksum_algo, k.d_src, k.src_offsets, k.num_partitions, k.d_dst,
@@ -218,6 +223,10 @@ int s3s_compress_map_outputs_batch(s3s_ctx* ctx, int codec, int checksum_algo, s
       d.out_checksums = k.out_checksums;
       in_off += al256(u[(size_t)t]);
       out_off += al256(cap[(size_t)t]);
+    }
+    if (enc_on(ctx)) {
+      ctx->iv_cur = call_ivs + 16 * (size_t)part0[(size_t)t0];
+      ctx->iv_cur_n = part0[(size_t)t1] - part0[(size_t)t0];
     }
     rc = s3s_compress_map_outputs_batch_device(ctx, codec, checksum_algo, dt.data(), t1 - t0);  // (synchronises ctx->stream)
     if (rc != S3S_OK && rc != S3S_E_CAPACITY) return rc;

@@ -29,6 +29,9 @@ enum BufId {
   B_ZSCRATCH, B_ZPIECES,  // zstd single pass: decoded partitions at guessed capacities, and the compaction's piece list
   B_ZENC,  // zstd map side: sequences + literals of the blocks in flight, one piece per resident workgroup
   B_TAILS,  // batched calls: one TaskTail per map task / fetched range (s3s_internal.h)
+  B_IVS,        // IO encryption, map side: one IV per partition of the call
+  B_CRYPT,      // IO encryption, reduce side: the fetched range decrypted, IVs dropped
+  B_CRYPT_OFF,  // IO encryption: stored / plain partition offsets of the AES-CTR pass where they are not B_INDEX
   B_COUNT
 };
 
@@ -71,6 +74,16 @@ struct s3s_ctx {
   bool hb_shared = false;  // hb_in / hb_out are the device's shared copy lanes (host_batch.hip: copy arbiter), not this context's to destroy
   hipEvent_t hb_ev_in[2] = {nullptr, nullptr}, hb_ev_out[2] = {nullptr, nullptr};
   double stage_ms[S3S_STAGE_COUNT] = {};
+  // Spark IO encryption (s3s_set_io_encryption): on while enc_rounds != 0.  The round keys live here on the host and travel
+  // to the AES-CTR kernel as arguments; they are wiped when the layer is switched off and in s3s_destroy
+  s3s::AesKeys enc_keys = {};
+  int enc_rounds = 0, enc_key_bits = 0;
+  bool enc_suspended = false;       // reduce side: the wrapped call on the decrypted bytes runs with the layer off
+  std::vector<uint8_t> ivs;         // s3s_set_stream_ivs: the IVs of the NEXT compress call (consumed by it, success or not)
+  bool ivs_set = false;
+  const uint8_t* iv_cur = nullptr;  // the IVs of the compress call (or task of a batch) in progress, iv_cur_n of them (-1: none given)
+  int64_t iv_cur_n = -1;
+  int iv_depth = 0;                 // entry points call each other: the outermost one owns the IVs
 };
 
 namespace s3s {
@@ -106,6 +119,44 @@ struct BatchVerdict {
     return rc;
   }
 };
+
+inline bool enc_on(const s3s_ctx* ctx) { return ctx && ctx->enc_rounds != 0 && !ctx->enc_suspended; }
+
+inline void wipe(void* p, size_t n) {
+  volatile uint8_t* v = static_cast<volatile uint8_t*>(p);
+  for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
+// Every compress entry point creates one: the outermost takes the IVs that s3s_set_stream_ivs left (they are gone when it
+// returns, whichever way), the nested ones see the slice their caller set in iv_cur / iv_cur_n.
+struct IvScope {
+  s3s_ctx* c;
+  std::vector<uint8_t> own;
+  explicit IvScope(s3s_ctx* ctx) : c(ctx) {
+    if (c->iv_depth++ != 0) return;
+    own.swap(c->ivs);
+    c->iv_cur = own.data();
+    c->iv_cur_n = c->ivs_set ? (int64_t)(own.size() / 16) : -1;
+    c->ivs_set = false;
+  }
+  ~IvScope() {
+    if (--c->iv_depth != 0) return;
+    c->iv_cur = nullptr;
+    c->iv_cur_n = -1;
+  }
+  IvScope(const IvScope&) = delete;
+  IvScope& operator=(const IvScope&) = delete;
+};
+
+// with the layer on, a compress call needs exactly one IV per partition (a call without partitions needs none)
+inline int enc_check_ivs(s3s_ctx* ctx, int64_t n_parts) {
+  if (!enc_on(ctx) || ctx->iv_cur_n == n_parts || (n_parts == 0 && ctx->iv_cur_n < 0)) return S3S_OK;
+  if (ctx->iv_cur_n < 0)
+    return fail(ctx, S3S_E_INVALID, "IO encryption is on and no IVs were set for this call (s3s_set_stream_ivs: one per partition, %lld)",
+                (long long)n_parts);
+  return fail(ctx, S3S_E_INVALID, "IO encryption is on: the call has %lld partitions, s3s_set_stream_ivs gave %lld IVs",
+              (long long)n_parts, (long long)ctx->iv_cur_n);
+}
 
 #define HIP_TRY(ctx, expr)                                                                  \
   do {                                                                                      \

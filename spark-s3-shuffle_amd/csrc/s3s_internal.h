@@ -53,7 +53,11 @@ enum : int32_t {
   // LZF map side (S3S_OPT_LZF_COMPRESS, lzf_compress.hip): one chunk of at most kLzfChunk bytes - the 7-byte ('Z' 'V' 1 | clen |
   // ulen) or 5-byte ('Z' 'V' 0 | len) header right-aligned in the slot header, the liblzf block from +32; item_size bit 31 =
   // stored chunk (bytes copied from the source)
-  kItemLzfChunk = 9
+  kItemLzfChunk = 9,
+  // Spark IO encryption (s3s_set_io_encryption, aes_ctr.hip): 16 bytes in front of the first item of every non-empty partition.
+  // The gather leaves them alone; the AES-CTR pass behind it writes the partition's IV there.  No codec kernel knows the
+  // kind: launch_seed_iv_items gives the records their item_size
+  kItemIv = 10
 };
 constexpr int kLzfChunk = 65535;          // source bytes of an LZFOutputStream chunk (= s3s_lzf_enc::kChunk)
 constexpr int kLzfSlotPayload = (kLzfChunk + kLzfChunk / 32 + 4 + 15) & ~15;  // the largest block the parse writes, rounded up
@@ -101,6 +105,25 @@ void launch_zstd_compress(const uint8_t* d_src, const Item* d_items, int32_t n_i
 // LZF: every kItemLzfChunk item into its slot (and its item_size); one wavefront per item
 void launch_lzf_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items, uint8_t* d_slots, int64_t slot_stride,
                          uint32_t* d_item_size, hipStream_t st);
+// ---- Spark IO encryption: AES-CTR over the stored bytes (aes_ctr.hip) ----------------------------------------------------
+struct AesKeys {
+  uint32_t rk[60];  // FIPS-197 round keys as big-endian words, 4 x (rounds + 1) of them in use; a kernel ARGUMENT, never in HBM
+};
+// rounds (10 / 12 / 14) for a key of 16 / 24 / 32 bytes, 0 (nothing written) for any other length
+int aes_expand_key(const uint8_t* key, int key_bytes, AesKeys* keys);
+enum { kCtrInPlace = 0, kCtrFromPlain = 1, kCtrDecrypt = 2 };
+// stored partition p = d_stored_off[p] .. d_stored_off[p + 1] (n_parts + 1 DEVICE offsets; a non-empty one is IV | cipher text)
+//   kCtrInPlace    d_out holds 16 free bytes + the plain bytes of every non-empty partition: writes d_ivs[16 p ..] and XORs in place
+//   kCtrFromPlain  plain partition p at d_in + d_plain_off[p]  ->  IV | cipher text at d_out + d_stored_off[p]
+//   kCtrDecrypt    stored bytes at d_in + d_stored_off[p]  ->  plain bytes at d_out + d_plain_off[p]; the IV is read from d_in
+// stored_bound: what the host knows d_stored_off[n] - d_stored_off[0] not to exceed (sizes the grid; at most aes_ctr_max_bytes());
+// stored_limit: no stored byte at or beyond this offset is touched whatever the device-side offsets say
+int64_t aes_ctr_max_bytes();
+void launch_aes_ctr(int mode, const AesKeys& keys, int rounds, const uint8_t* d_in, uint8_t* d_out, const int64_t* d_stored_off,
+                    const int64_t* d_plain_off, const uint8_t* d_ivs, int32_t n_parts, int64_t stored_bound, int64_t stored_limit,
+                    hipStream_t st);
+// item_size = 16 for every kItemIv record (between the codec kernels and the scan)
+void launch_seed_iv_items(const Item* d_items, int32_t n_items, uint32_t* d_item_size, hipStream_t st);
 // exclusive scan of item sizes + partition index extraction
 void launch_scan_items(const Item* d_items, const uint32_t* d_item_size, int32_t n_items,
                        int64_t* d_item_off, const int32_t* d_part_first, int32_t n_parts,

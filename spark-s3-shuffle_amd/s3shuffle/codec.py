@@ -22,6 +22,7 @@ OPT_LZ4_BLOCK_SIZE_LARGE = 8  # ABI 10: spark.io.compression.lz4.blockSize 64 ..
 
 OPT_ZSTD_COMPRESS = 9  # ABI 11: 1 = write decode-compatible Zstandard frames on the map side (not libzstd's bytes); default 0
 OPT_LZF_COMPRESS = 10  # ABI 11, additive key: 1 = write decode-compatible LZF streams on the map side (not compress-lzf's bytes); default 0
+OPT_IO_ENCRYPTION_KEY_BITS = 11  # ABI 11, additive, read-only: 0 / 128 / 192 / 256 - the key Codec.set_io_encryption holds
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
 STATUS_NOT_RUN = -100  # per-entry status of a batch call that failed as a call before this entry had a verdict (ABI 6)
@@ -140,6 +141,9 @@ def load_library() -> ctypes.CDLL:
     lib.s3s_host_alloc.restype = vp
     lib.s3s_host_alloc.argtypes = [ctypes.c_int64]
     lib.s3s_host_free.argtypes = [vp]
+    if hasattr(lib, "s3s_set_io_encryption"):  # (S3S_CODEC_LIB may name an older build of the library)
+        lib.s3s_set_io_encryption.argtypes = [vp, vp, ctypes.c_int32]
+        lib.s3s_set_stream_ivs.argtypes = [vp, vp, ctypes.c_int64]
     _LIB = lib
     return lib
 
@@ -203,6 +207,25 @@ class Codec:
 
     def get_option(self, key: int) -> int:
         return int(self._lib.s3s_get_option(self._h, key))
+
+    def set_io_encryption(self, key: Optional[bytes]):
+        """Spark IO encryption (AES/CTR/NoPadding) as a layer on both sides of the codec: a key of 16, 24 or 32 bytes switches
+        it on for every later call of this context, None (or b"") switches it off and wipes the key."""
+        key = bytes(key) if key else b""
+        self._check(self._lib.s3s_set_io_encryption(self._h, key if key else None, len(key)))
+
+    def set_stream_ivs(self, ivs):
+        """One 16-byte IV per PARTITION of the NEXT compress call (task by task, then partition by partition; the entry of an
+        empty partition is not used): bytes or a uint8 array of 16 * n bytes.  That call consumes them.  Never reusing an IV
+        under one key is the caller's duty."""
+        a = np.ascontiguousarray(np.frombuffer(ivs, dtype=np.uint8) if isinstance(ivs, (bytes, bytearray)) else ivs, dtype=np.uint8).reshape(-1)
+        if a.size % 16:
+            raise ValueError("IVs are 16 bytes each")
+        self._check(self._lib.s3s_set_stream_ivs(self._h, a.ctypes.data if a.size else None, a.size // 16))
+
+    @property
+    def io_encryption_key_bits(self) -> int:
+        return self.get_option(OPT_IO_ENCRYPTION_KEY_BITS)
 
     def stage_ms(self, stage: int) -> float:
         return float(self._lib.s3s_stage_ms(self._h, stage))
@@ -340,7 +363,12 @@ class Codec:
             cap = out.size if dst_capacity is None else int(dst_capacity)
             dst = out
         else:
-            cap = self.decompressed_size(codec, comp) if dst_capacity is None else int(dst_capacity)
+            if dst_capacity is not None:
+                cap = int(dst_capacity)
+            elif self.get_option(OPT_IO_ENCRYPTION_KEY_BITS) > 0:  # every partition is a stream of its own, IV first
+                cap = sum(self.decompressed_size(codec, comp[offs[p]:offs[p + 1]]) for p in range(n))
+            else:
+                cap = self.decompressed_size(codec, comp)
             dst = np.empty(max(cap, 1), dtype=np.uint8)
         out_len = ctypes.c_int64(0)
         bad = ctypes.c_int32(-1)
