@@ -377,6 +377,78 @@ int s3s_compress_map_output_segments_device(s3s_ctx* ctx, int codec, int checksu
                                             uint8_t* d_dst, int64_t dst_capacity, int64_t* out_index,
                                             int64_t* out_checksums, int64_t* out_total);
 
+/* java.util.zip.Checksum continued (ABI 11, additive: detect by the symbols): out[i] = the checksum state after
+ * data[offsets[i], offsets[i+1]) when it was seeds[i] before - seeds[i] is getValue() of the bytes so far (a fresh Adler32 is 1, a
+ * fresh CRC32 / CRC32C is 0).  seeds == NULL: every range starts fresh, and the call is s3s_checksum_ranges*.  A range of no
+ * bytes returns its seed.  This is what S3ChecksumValidationStream.scala:54-66 does with one Checksum object across reads. */
+int s3s_checksum_ranges_seeded(s3s_ctx* ctx, int checksum_algo, const uint8_t* data, const int64_t* offsets, int32_t n,
+                               const int64_t* seeds, int64_t* out);
+int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uint8_t* d_data, const int64_t* offsets, int32_t n,
+                                      const int64_t* seeds, int64_t* out);
+
+/* ---- reduce side, streaming: a fetched range decoded window by window, in bounded memory --------------------------------
+ * (ABI 11, additive: callers detect support by the symbols.)  s3s_decompress_range* needs the whole compressed range and the
+ * whole decoded range resident at once.  The reference never holds a block like that: storage/S3BufferedInputStreamAdaptor
+ * .scala:13-19 buffers min(maxBufferSizeTask, block length), storage/S3ChecksumValidationStream.scala:54-86 validates a
+ * partition as its last byte streams past, and the codec input streams decode frame by frame.  An s3s_dstream gives a range of
+ * any size that shape: the caller feeds windows of the compressed bytes and gets the decoded bytes of the whole units in each.
+ *
+ * Window   comp[0, comp_len) holds the bytes of the range that start at s3s_dstream_position(); the caller presents again what
+ *          the previous feed did not consume.  A window that reaches past part_offsets[nparts] is S3S_E_INVALID.
+ * Unit     an LZ4Block frame (the 21-byte end frame included); a Snappy 16-byte stream header or one length | chunk; an LZF
+ *          'Z' 'V' chunk; for S3S_CODEC_NONE a byte.
+ * A feed   takes the longest prefix of whole units that lies inside the window and whose decoded bytes fit dst_capacity, and
+ *          decodes them to dst[0, out_len).  Concatenated streams inside a partition (multi-spill) work as in the one-shot call.
+ * Progress a feed consumes at least one unit when the window holds the whole first unit and dst_capacity is at least its
+ *          decoded size.  Otherwise:  the unit is not whole in the window - S3S_OK, consumed = 0, need_comp set (two steps at
+ *          the most for LZ4 and Snappy: the header's length, then header + payload; LZF's compressed chunk header adds a
+ *          third);  the unit does not fit dst - S3S_E_CAPACITY, need_dst set, nothing consumed, the stream stays usable;  the
+ *          unit is not whole and the window already ends at the end of the range - S3S_E_BAD_FRAME (truncated).
+ * Checksum the state of the open partition is carried from feed to feed, over consumed bytes only.  A partition is verified in
+ *          the feed that consumes its last byte, an empty partition as the position passes it, and that feed's decode is
+ *          launched only after the verdict: on a mismatch the feed returns S3S_E_CHECKSUM with bad_partition, consumed = 0
+ *          and out_len = 0.  NOTE: the decoded bytes of a partition that is still open are handed out BEFORE its checksum is
+ *          known - exactly what S3ChecksumValidationStream does (it raises at the partition's end); a caller that must not
+ *          act on unverified bytes holds them back until the feed that passes the partition's end has returned S3S_OK.
+ *          NOTE: the one-shot call reports a wrong checksum before a corrupt frame.  A feed does so for the partitions whose
+ *          last byte its window holds; a corrupt frame in a partition that is still open is reported first, as
+ *          S3S_E_BAD_FRAME, by the feed that meets it.
+ * Errors   stick: after S3S_E_CHECKSUM or S3S_E_BAD_FRAME every later feed returns the same code (and bad_partition).
+ * Result   the concatenation of all dst outputs is what s3s_decompress_range_device writes for the same range, and the final
+ *          verdict falls in the same class.
+ * State    a stream holds host state only (position, carried checksum, verdicts; whether the position is inside a Snappy
+ *          stream follows from it) and no device memory between feeds: a feed works in the context's workspace, and other
+ *          calls on the same context may run between two feeds.  The context stays single-threaded and must outlive the
+ *          stream.  s3s_dstream_feed (host buffers) stages the window and dst_capacity bytes of output in that workspace:
+ *          the caller's two sizes are the memory bound.
+ * Refused  at open with S3S_E_UNSUPPORTED, context intact: S3S_CODEC_ZSTD (a frame is a whole partition with history across
+ *          its blocks and, from zstd-jni's streaming writer, no content size: resumable Zstandard is separate work) and any
+ *          context with IO encryption on (the key stream would have to be sought mid-partition).  Both keep the one-shot
+ *          call.  S3S_OPT_LZ4_DECODE_VARIANT = 3 WORKS: a feed launches whichever decoder the option names.
+ * Not here a streaming map side, a reader in the C++ host mirror, a batched feed of several streams. */
+typedef struct s3s_dstream s3s_dstream;
+typedef struct s3s_dstream_result {
+  int64_t consumed;      /* bytes of this window taken; the next window starts there */
+  int64_t out_len;       /* decoded bytes written to dst by this feed */
+  int64_t need_comp;     /* consumed == 0 because the first unit is not whole in the window: the smallest window length known
+                            to hold it (header + payload when the header is in the window, else the header's length); else 0 */
+  int64_t need_dst;      /* S3S_E_CAPACITY: decoded size of the first unit; 0 otherwise */
+  int32_t bad_partition; /* S3S_E_CHECKSUM: range-relative partition, else -1 */
+  int32_t at_end;        /* 1: position == range length and every partition verified */
+} s3s_dstream_result;
+/* part_offsets[nparts + 1] (part_offsets[0] == 0) and ref_checksums[nparts] (may be NULL iff checksum NONE) are copied.  Like
+ * every entry point this one returns the code; the stream comes back through *out (NULL on failure). */
+int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
+                     int32_t nparts, s3s_dstream** out);
+int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_len, uint8_t* d_dst, int64_t dst_capacity,
+                            s3s_dstream_result* r);
+int s3s_dstream_feed(s3s_dstream* s, const uint8_t* comp, int64_t comp_len, uint8_t* dst, int64_t dst_capacity, /* host buffers */
+                     s3s_dstream_result* r);
+int64_t s3s_dstream_position(const s3s_dstream* s);
+/* Frees the stream.  S3S_OK at the end of the range with every partition verified; the stream's error when it has one;
+ * S3S_E_BAD_FRAME when the range was not read to its end (what a reader sees that closes a truncated stream). */
+int s3s_dstream_close(s3s_dstream* s);
+
 /* Page-locked host staging memory for the host-buffer entry points (no reference counterpart:
  * it replaces the heap byte[] of storage/S3BufferedInputStreamAdaptor.scala:13-19 — one
  * BufferedInputStream of min(maxBufferSizeTask, block length) bytes per prefetched block — and of

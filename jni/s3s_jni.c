@@ -324,3 +324,83 @@ JNIEXPORT jint JNICALL FN(decompressRangesBatch)(JNIEnv* e, jclass c, jlong h, j
   free(r);
   return rc;
 }
+
+/* ---- streaming reduce side: a fetched range decoded window by window (s3s_dstream_*; S3GpuStreamingInputStream) -------
+ * and the seeded checksums under it.  WEAK like the IO encryption symbols: against a libs3shuffle_codec.so from before the
+ * streams the natives answer S3S_E_UNSUPPORTED, the answer S3GpuBlockDecoder uses to keep the JVM path for large ranges.
+ * A stream travels as a jlong; the window is comp[compOff, compOff + compLen) of a direct buffer, so the caller presents
+ * what a feed did not consume without moving it.  out = { consumed, out_len, need_comp, need_dst, bad_partition, at_end }. */
+extern int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
+                            int32_t nparts, s3s_dstream** out) __attribute__((weak));
+extern int s3s_dstream_feed(s3s_dstream* s, const uint8_t* comp, int64_t comp_len, uint8_t* dst, int64_t dst_capacity,
+                            s3s_dstream_result* r) __attribute__((weak));
+extern int64_t s3s_dstream_position(const s3s_dstream* s) __attribute__((weak));
+extern int s3s_dstream_close(s3s_dstream* s) __attribute__((weak));
+extern int s3s_checksum_ranges_seeded(s3s_ctx* ctx, int checksum_algo, const uint8_t* data, const int64_t* offsets, int32_t n,
+                                      const int64_t* seeds, int64_t* out) __attribute__((weak));
+#define STREAM(s) ((s3s_dstream*)(intptr_t)(s))
+
+JNIEXPORT jint JNICALL FN(dstreamOpen)(JNIEnv* e, jclass c, jlong h, jint codec, jint algo, jlongArray partOffsets,
+                                       jlongArray refChecksums, jint nparts, jlongArray outStream) {
+  (void)c;
+  if (!s3s_dstream_open) return S3S_E_UNSUPPORTED;
+  if (!outStream || (*e)->GetArrayLength(e, outStream) < 1) return S3S_E_INVALID;
+  if (partOffsets && (*e)->GetArrayLength(e, partOffsets) < nparts + 1) return S3S_E_INVALID; /* (the library reads nparts + 1 / nparts entries) */
+  if (refChecksums && (*e)->GetArrayLength(e, refChecksums) < nparts) return S3S_E_INVALID;
+  jlong *po = pin(e, partOffsets), *rs = pin(e, refChecksums), *os = pin(e, outStream);
+  s3s_dstream* s = NULL;
+  const int rc = s3s_dstream_open(CTX(h), codec, algo, (const int64_t*)po, (const int64_t*)rs, nparts, &s);
+  os[0] = (jlong)(intptr_t)s;
+  unpin(e, partOffsets, po, JNI_ABORT);
+  unpin(e, refChecksums, rs, JNI_ABORT);
+  unpin(e, outStream, os, 0);
+  return rc;
+}
+JNIEXPORT jint JNICALL FN(dstreamFeed)(JNIEnv* e, jclass c, jlong stream, jobject comp, jlong compOff, jlong compLen,
+                                       jobject dst, jlong dstCap, jlongArray out) {
+  (void)c;
+  if (!s3s_dstream_feed) return S3S_E_UNSUPPORTED;
+  if (!out || (*e)->GetArrayLength(e, out) < 6 || compOff < 0 || compLen < 0 || dstCap < 0) return S3S_E_INVALID;
+  /* the library copies compLen bytes in and up to dstCap bytes out: both must lie inside the buffers they name */
+  if ((compLen > 0 || compOff > 0) && (!comp || compOff > (*e)->GetDirectBufferCapacity(e, comp) - compLen)) return S3S_E_INVALID;
+  if (dstCap > 0 && (!dst || dstCap > (*e)->GetDirectBufferCapacity(e, dst))) return S3S_E_INVALID;
+  uint8_t* cp = addr(e, comp);
+  s3s_dstream_result r = {0, 0, 0, 0, -1, 0};
+  const int rc = s3s_dstream_feed(STREAM(stream), cp ? cp + compOff : NULL, compLen, addr(e, dst), dstCap, &r);
+  jlong* o = pin(e, out);
+  o[0] = r.consumed;
+  o[1] = r.out_len;
+  o[2] = r.need_comp;
+  o[3] = r.need_dst;
+  o[4] = r.bad_partition;
+  o[5] = r.at_end;
+  unpin(e, out, o, 0);
+  return rc;
+}
+JNIEXPORT jlong JNICALL FN(dstreamPosition)(JNIEnv* e, jclass c, jlong stream) {
+  (void)e; (void)c;
+  return s3s_dstream_position ? s3s_dstream_position(STREAM(stream)) : (jlong)S3S_E_UNSUPPORTED;
+}
+JNIEXPORT jint JNICALL FN(dstreamClose)(JNIEnv* e, jclass c, jlong stream) {
+  (void)e; (void)c;
+  return s3s_dstream_close ? s3s_dstream_close(STREAM(stream)) : S3S_E_UNSUPPORTED;
+}
+JNIEXPORT jint JNICALL FN(checksumRangesSeeded)(JNIEnv* e, jclass c, jlong h, jint algo, jobject data, jlongArray offsets,
+                                                jint n, jlongArray seeds, jlongArray out) {
+  (void)c;
+  if (!s3s_checksum_ranges_seeded) return S3S_E_UNSUPPORTED;
+  if (n < 0 || !offsets || (*e)->GetArrayLength(e, offsets) < n + 1 || !out || (*e)->GetArrayLength(e, out) < n) return S3S_E_INVALID;
+  if (seeds && (*e)->GetArrayLength(e, seeds) < n) return S3S_E_INVALID;
+  jlong *of = pin(e, offsets), *sd = pin(e, seeds), *o = pin(e, out);
+  if (n > 0 && (of[n] < 0 || !data || of[n] > (*e)->GetDirectBufferCapacity(e, data))) { /* (the library checks the order) */
+    unpin(e, offsets, of, JNI_ABORT);
+    unpin(e, seeds, sd, JNI_ABORT);
+    unpin(e, out, o, JNI_ABORT);
+    return S3S_E_INVALID;
+  }
+  const int rc = s3s_checksum_ranges_seeded(CTX(h), algo, addr(e, data), (const int64_t*)of, n, (const int64_t*)sd, (int64_t*)o);
+  unpin(e, offsets, of, JNI_ABORT);
+  unpin(e, seeds, sd, JNI_ABORT);
+  unpin(e, out, o, 0);
+  return rc;
+}

@@ -76,6 +76,19 @@ object S3SCodec {
                                     dst: Array[ByteBuffer], dstCap: Array[Long], outLen: Array[Long],
                                     outBadPartition: Array[Int], outStatus: Array[Int]): Int
 
+  // streaming reduce side (s3s_dstream_*: a range of any size decoded window by window, S3GpuStreamingInputStream) and the
+  // seeded checksums under it.  A stream is a Long; the window is comp[compOff, compOff + compLen) of a direct buffer;
+  // out = { consumed, out_len, need_comp, need_dst, bad_partition, at_end }.  E_UNSUPPORTED: a library from before the streams,
+  // a Zstandard range, or a context with IO encryption on - the caller keeps the JVM path.
+  @native def dstreamOpen(handle: Long, codec: Int, algo: Int, partOffsets: Array[Long], refChecksums: Array[Long],
+                          nparts: Int, outStream: Array[Long]): Int
+  @native def dstreamFeed(stream: Long, comp: ByteBuffer, compOff: Long, compLen: Long, dst: ByteBuffer, dstCap: Long,
+                          out: Array[Long]): Int
+  @native def dstreamPosition(stream: Long): Long
+  @native def dstreamClose(stream: Long): Int
+  @native def checksumRangesSeeded(handle: Long, algo: Int, data: ByteBuffer, offsets: Array[Long], n: Int,
+                                   seeds: Array[Long], out: Array[Long]): Int
+
   // ---- loading + per-thread contexts -------------------------------------------------------------------------------
   @volatile private var loaded = false
 

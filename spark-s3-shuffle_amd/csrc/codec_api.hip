@@ -962,8 +962,8 @@ int s3s_compress_map_output(s3s_ctx* ctx, int codec, int checksum_algo, const ui
   return S3S_OK;
 }
 
-int s3s_checksum_ranges_device(s3s_ctx* ctx, int algo, const uint8_t* d_data,
-                               const int64_t* offsets, int32_t n, int64_t* out) {
+int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int algo, const uint8_t* d_data, const int64_t* offsets, int32_t n,
+                                      const int64_t* seeds, int64_t* out) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   if (n < 0 || !offsets || (n > 0 && !out)) return fail(ctx, S3S_E_INVALID, "null offsets/out or negative count");
@@ -976,11 +976,12 @@ int s3s_checksum_ranges_device(s3s_ctx* ctx, int algo, const uint8_t* d_data,
   const size_t off_bytes = sizeof(int64_t) * (size_t)(n + 1), seg_bytes = sizeof(int32_t) * (size_t)(n + 1);
   const size_t o_seg = (off_bytes + 15) & ~size_t(15), o_out = (o_seg + seg_bytes + 15) & ~size_t(15);
   int rc;
-  if ((rc = ensure_stage(ctx, o_out + sizeof(int64_t) * (size_t)n))) return rc;
+  if ((rc = ensure_stage(ctx, o_out + sizeof(int64_t) * (size_t)n * (seeds ? 2 : 1)))) return rc;
   uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
   int64_t* h_off = reinterpret_cast<int64_t*>(hs);
   int32_t* h_seg = reinterpret_cast<int32_t*>(hs + o_seg);
   int64_t* h_out = reinterpret_cast<int64_t*>(hs + o_out);
+  int64_t* h_seeds = h_out + n;  // (seeded form only)
   int64_t segs = 0;
   for (int32_t p = 0; p < n; p++) {
     h_off[p] = offsets[p];
@@ -995,6 +996,14 @@ int s3s_checksum_ranges_device(s3s_ctx* ctx, int algo, const uint8_t* d_data,
   HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_OFFSETS].p, h_off, off_bytes, hipMemcpyHostToDevice, ctx->stream));
   record(ctx, 0);
   if ((rc = run_checksum(ctx, algo, d_data, dev<int64_t>(ctx, B_OFFSETS), n, h_seg, dev<int64_t>(ctx, B_SUMS), offsets[n]))) return rc;
+  if (seeds) {  // one more leading term per range, behind the launch that is the unseeded call's
+    if ((rc = ensure(ctx, B_REF_SUMS, sizeof(int64_t) * (size_t)n))) return rc;
+    memcpy(h_seeds, seeds, sizeof(int64_t) * (size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_REF_SUMS].p, h_seeds, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    launch_checksum_seed(algo, dev<int64_t>(ctx, B_OFFSETS), n, ctx->buf[B_TABLES].p, dev<int64_t>(ctx, B_REF_SUMS),
+                         dev<int64_t>(ctx, B_SUMS), ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+  }
   record(ctx, 3);
   HIP_TRY(ctx, hipMemcpyAsync(h_out, ctx->buf[B_SUMS].p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1008,8 +1017,13 @@ int s3s_checksum_ranges_device(s3s_ctx* ctx, int algo, const uint8_t* d_data,
   return S3S_OK;
 }
 
-int s3s_checksum_ranges(s3s_ctx* ctx, int algo, const uint8_t* data, const int64_t* offsets,
-                        int32_t n, int64_t* out) {
+int s3s_checksum_ranges_device(s3s_ctx* ctx, int algo, const uint8_t* d_data,
+                               const int64_t* offsets, int32_t n, int64_t* out) {
+  return s3s_checksum_ranges_seeded_device(ctx, algo, d_data, offsets, n, nullptr, out);
+}
+
+int s3s_checksum_ranges_seeded(s3s_ctx* ctx, int algo, const uint8_t* data, const int64_t* offsets, int32_t n,
+                               const int64_t* seeds, int64_t* out) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   if (n < 0 || !offsets) return fail(ctx, S3S_E_INVALID, "null offsets or negative count");
@@ -1023,7 +1037,12 @@ int s3s_checksum_ranges(s3s_ctx* ctx, int algo, const uint8_t* data, const int64
     HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_SRC].p, data + first, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
   std::vector<int64_t> rebased((size_t)n + 1);
   for (int32_t p = 0; p <= n; p++) rebased[(size_t)p] = offsets[p] - first;
-  return s3s_checksum_ranges_device(ctx, algo, dev<uint8_t>(ctx, B_SRC), rebased.data(), n, out);
+  return s3s_checksum_ranges_seeded_device(ctx, algo, dev<uint8_t>(ctx, B_SRC), rebased.data(), n, seeds, out);
+}
+
+int s3s_checksum_ranges(s3s_ctx* ctx, int algo, const uint8_t* data, const int64_t* offsets,
+                        int32_t n, int64_t* out) {
+  return s3s_checksum_ranges_seeded(ctx, algo, data, offsets, n, nullptr, out);
 }
 
 #ifdef S3S_LZ4_TIMING

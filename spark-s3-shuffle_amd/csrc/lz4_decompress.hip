@@ -20,6 +20,7 @@
 // then one wavefront per frame decodes it: the batch decoder (lz4_decode_batch.hip, default) or the ring decoder
 // below (S3S_OPT_LZ4_DECODE_VARIANT 3); frame hashes are checked by lz4_verify_frames_kernel / in the ring kernel.
 #include "s3s_internal.h"
+#include "discover_core.h"
 
 #ifdef S3S_LZ4_TIMING
 __device__ unsigned long long g_dec_dbg[16];
@@ -32,42 +33,6 @@ __device__ unsigned long long g_dec_dbg[16];
 
 namespace s3s {
 namespace {
-
-constexpr int kTileBytes = 65536;
-constexpr uint64_t kMagic = 0x6b636f6c42345a4cull;  // "LZ4Block" little-endian
-
-__device__ __forceinline__ uint64_t ld64u(const uint8_t* p) {
-  uint64_t v;
-  __builtin_memcpy(&v, p, 8);
-  return v;
-}
-__device__ __forceinline__ uint32_t ld32u(const uint8_t* p) {
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return v;
-}
-
-struct Header {
-  int32_t method, comp_len, orig_len;
-  uint32_t check;
-  bool ok;
-};
-
-// LZ4BlockInputStream.refill() header checks (magic excluded)
-__device__ __forceinline__ Header parse_header(const uint8_t* h) {
-  Header r;
-  const uint32_t token = h[8];
-  r.method = (int32_t)(token & 0xF0u);
-  const int level = 10 + (int)(token & 0x0Fu);
-  r.comp_len = (int32_t)ld32u(h + 9);
-  r.orig_len = (int32_t)ld32u(h + 13);
-  r.check = ld32u(h + 17);
-  r.ok = (r.method == 0x10 || r.method == 0x20) && r.orig_len >= 0 && r.comp_len >= 0 &&
-         r.orig_len <= (1 << level) && !(r.orig_len == 0 && r.comp_len != 0) &&
-         !(r.orig_len != 0 && r.comp_len == 0) && !(r.method == 0x10 && r.orig_len != r.comp_len) &&
-         !(r.orig_len == 0 && r.check != 0);
-  return r;
-}
 
 // Sequential walk (one lane) from `pos` until the chain leaves [.., tile_end) or reaches
 // comp_len.  Returns the exit position, or -1 on a malformed header / overrun.  Optionally
@@ -662,6 +627,13 @@ void launch_lz4_emit_frames(const uint8_t* d_comp, int64_t comp_len, int32_t n_t
                      d_frame_orig, d_status);
   hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(kWave), 0, st, d_frame_orig, n_frames,
                      d_frame_out);
+}
+
+void launch_lz4_speculate(const uint8_t* d_comp, int64_t comp_len, int32_t n_tiles, int64_t* d_spec_entry, int64_t* d_spec_exit,
+                          int32_t* d_spec_count, hipStream_t st) {
+  if (n_tiles <= 0) return;
+  hipLaunchKernelGGL(tile_speculate_kernel, dim3((unsigned)n_tiles), dim3(kWave), 0, st, d_comp, comp_len, n_tiles, d_spec_entry,
+                     d_spec_exit, d_spec_count);
 }
 
 void launch_lz4_discover_batch(const LzRange* d_ranges, int32_t n_ranges, const int32_t* d_tile_range,

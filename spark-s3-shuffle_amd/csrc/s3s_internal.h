@@ -258,6 +258,39 @@ void launch_snappy_decompress(const uint8_t* d_comp, const Frame* d_frames, int3
                               int variant, hipStream_t st, int chunk_format = kChunkSnappy);
 void launch_scan_u32(const uint32_t* d_in, int64_t n, int64_t* d_out, hipStream_t st);
 
+// ---- streaming reduce side (decode_stream.hip: s3s_dstream_feed*) ----------------------------------------------------------
+// The window comp[0, comp_len) starts on a unit boundary of the range and may end inside a unit; range_left >= comp_len is
+// what the RANGE still holds from the window's start.  A unit that crosses comp_len ends the chain there (d_result[0] = the
+// stop offset, d_result[1] = the unit's length as far as the window shows it: header + payload when the header is whole,
+// else the header's length; 0 when the chain ends on a unit boundary); one that crosses range_left too, and anything
+// malformed, raises *d_status as in the one-shot kernels.  No byte at or beyond comp_len is read.
+//   LZ4Block: the one-shot speculation (launch_lz4_speculate), then a resolve that stops instead of failing, then the scan of
+//   the tile counts (d_frame_base[n_tiles] = frames in front of the stop).  The frames are emitted by launch_lz4_emit_frames with the stop
+//   offset as comp_len.
+void launch_lz4_speculate(const uint8_t* d_comp, int64_t comp_len, int32_t n_tiles, int64_t* d_spec_entry, int64_t* d_spec_exit,
+                          int32_t* d_spec_count, hipStream_t st);
+void launch_lz4_discover_stream(const uint8_t* d_comp, int64_t comp_len, int64_t range_left, int32_t n_tiles,
+                                int64_t* d_spec_entry, int64_t* d_spec_exit, int32_t* d_spec_count, int64_t* d_true_entry,
+                                int64_t* d_frame_base, int32_t* d_status, int64_t* d_result, hipStream_t st);
+//   Snappy / LZF: d_piece_off[n_pieces + 1] are the pieces of partitions inside the window (window-relative).  Piece 0
+//   starts inside a Snappy stream when first_mid != 0 (no stream header expected there); the partition of the last piece
+//   ends at last_pend >= d_piece_off[n_pieces] (beyond the window: its last unit may be cut).
+void launch_snappy_count_frames_stream(const uint8_t* d_comp, const int64_t* d_piece_off, int32_t n_pieces, int32_t first_mid,
+                                       int64_t last_pend, uint32_t* d_piece_nframes, int32_t* d_status, int64_t* d_result,
+                                       hipStream_t st, int chunk_format);
+void launch_snappy_emit_frames_stream(const uint8_t* d_comp, const int64_t* d_piece_off, int32_t n_pieces, int32_t first_mid,
+                                      int64_t last_pend, const int64_t* d_frame_base, Frame* d_frames, uint32_t* d_frame_orig,
+                                      int32_t* d_status, hipStream_t st, int chunk_format);
+//   The cut of a frame table at the caller's output capacity, behind the scan of the decoded sizes: k = the largest index
+//   with d_frame_out[k] <= dst_capacity.  d_result = {k, consumed, out_len, need}: consumed = where unit k starts (the stop
+//   offset when k == n_frames), out_len = d_frame_out[k], need = decoded bytes of frame k (0 when k == n_frames).
+void launch_frames_cut(int codec, const Frame* d_frames, const uint32_t* d_frame_orig, const int64_t* d_frame_out, int64_t n_frames,
+                       int64_t dst_capacity, int64_t stop, int64_t* d_result, hipStream_t st);
+//   java.util.zip.Checksum continued: d_out[i] (the checksum of range i alone) becomes the state after range i when it was
+//   d_seeds[i] before (getValue() of the bytes so far) - the combine identities with the seed as one more leading term.
+void launch_checksum_seed(int algo, const int64_t* d_offsets, int32_t n, const void* d_tables, const int64_t* d_seeds,
+                          int64_t* d_out, hipStream_t st);
+
 // ---- device helpers shared by several kernels --------------------------------------------
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) {
   return __builtin_amdgcn_alignbit(x, x, 32 - r);

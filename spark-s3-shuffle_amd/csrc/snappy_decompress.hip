@@ -6,15 +6,11 @@
 // i32 BE compressedLength | raw snappy per chunk; concatenated streams are accepted, which is
 // what makes batch fetch and multi-spill merge legal, S3ShuffleReader.scala:55-75).
 #include "s3s_internal.h"
+#include "discover_core.h"
 
 namespace s3s {
 namespace {
 
-
-__device__ __forceinline__ bool is_stream_header(const uint8_t* c) {
-  return c[0] == 0x82 && c[1] == 'S' && c[2] == 'N' && c[3] == 'A' && c[4] == 'P' && c[5] == 'P' &&
-         c[6] == 'Y' && c[7] == 0;
-}
 
 // LZFInputStream (compress-lzf) framing: 'Z' 'V' 0 | len u16 BE | bytes   or   'Z' 'V' 1 | clen u16 BE | ulen u16 BE | LZF block;
 // chunks until the end of the partition (concatenated streams are simply more chunks).

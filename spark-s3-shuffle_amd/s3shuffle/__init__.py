@@ -18,6 +18,7 @@ from .codec import (  # noqa: F401
     CODEC_ZSTD,
     Codec,
     CodecError,
+    DecodeStream,
     PinnedBuffer,
     device_count,
     library_path,

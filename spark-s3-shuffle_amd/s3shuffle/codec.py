@@ -77,6 +77,12 @@ class FetchRange(ctypes.Structure):
                 ("out_len", ctypes.c_int64), ("bad_partition", ctypes.c_int32), ("status", ctypes.c_int32)]
 
 
+class StreamResult(ctypes.Structure):
+    """s3s_dstream_result (include/s3shuffle_codec.h): what one feed of a DecodeStream did."""
+    _fields_ = [("consumed", ctypes.c_int64), ("out_len", ctypes.c_int64), ("need_comp", ctypes.c_int64),
+                ("need_dst", ctypes.c_int64), ("bad_partition", ctypes.c_int32), ("at_end", ctypes.c_int32)]
+
+
 def load_library() -> ctypes.CDLL:
     """Loads the HIP codec library.  Fails loudly if it has not been built."""
     global _LIB
@@ -144,6 +150,17 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "s3s_set_io_encryption"):  # (S3S_CODEC_LIB may name an older build of the library)
         lib.s3s_set_io_encryption.argtypes = [vp, vp, ctypes.c_int32]
         lib.s3s_set_stream_ivs.argtypes = [vp, vp, ctypes.c_int64]
+    if hasattr(lib, "s3s_dstream_open"):  # streaming reduce side + seeded checksums (additive, ABI 11)
+        seeded_args = [vp, ctypes.c_int, vp, c_i64p, ctypes.c_int32, c_i64p, c_i64p]
+        lib.s3s_checksum_ranges_seeded.argtypes = seeded_args
+        lib.s3s_checksum_ranges_seeded_device.argtypes = seeded_args
+        lib.s3s_dstream_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, c_i64p, c_i64p, ctypes.c_int32, ctypes.POINTER(vp)]
+        feed_args = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.POINTER(StreamResult)]
+        lib.s3s_dstream_feed.argtypes = feed_args
+        lib.s3s_dstream_feed_device.argtypes = feed_args
+        lib.s3s_dstream_position.restype = ctypes.c_int64
+        lib.s3s_dstream_position.argtypes = [vp]
+        lib.s3s_dstream_close.argtypes = [vp]
     _LIB = lib
     return lib
 
@@ -345,7 +362,36 @@ class Codec:
         self._check(self._lib.s3s_checksum_ranges_device(self._h, algo, ctypes.c_void_p(d_data), _p64(offs), n, _p64(out)))
         return out[:n]
 
+    def checksum_ranges_seeded(self, algo: int, data: np.ndarray, offsets, seeds=None) -> np.ndarray:
+        """java.util.zip.Checksum continued: out[i] = the state after data[offsets[i]:offsets[i+1]] when it was seeds[i]
+        before (getValue() of the bytes so far; None: fresh).  Host buffer."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = _i64(offsets)
+        n = len(offs) - 1
+        sd = _i64(seeds) if seeds is not None else None
+        if sd is not None and sd.size != n:
+            raise ValueError("one seed per range")
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self._lib.s3s_checksum_ranges_seeded(self._h, algo, data.ctypes.data, _p64(offs), n,
+                                                         _p64(sd) if sd is not None else None, _p64(out)))
+        return out[:n]
+
+    def checksum_ranges_seeded_device(self, algo: int, d_data: int, offsets, seeds=None) -> np.ndarray:
+        offs = _i64(offsets)
+        n = len(offs) - 1
+        sd = _i64(seeds) if seeds is not None else None
+        if sd is not None and sd.size != n:
+            raise ValueError("one seed per range")
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self._lib.s3s_checksum_ranges_seeded_device(self._h, algo, ctypes.c_void_p(d_data), _p64(offs), n,
+                                                                _p64(sd) if sd is not None else None, _p64(out)))
+        return out[:n]
+
     # ---- reduce side ---------------------------------------------------------------------------
+    def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None) -> "DecodeStream":
+        """A fetched range decoded window by window in bounded memory (s3s_dstream_*)."""
+        return DecodeStream(self, codec, checksum, part_offsets, ref_checksums)
+
     def decompressed_size(self, codec: int, comp: np.ndarray) -> int:
         comp = np.ascontiguousarray(comp, dtype=np.uint8)
         out = ctypes.c_int64(0)
@@ -424,6 +470,80 @@ class Codec:
             bad = next((i for i, o in enumerate(out) if o[0] != 0), -1)
             self._check(rc, out[bad][2] if bad >= 0 else -1)
         return out
+
+
+class DecodeStream:
+    """One s3s_dstream: the streaming reduce side.  `feed` / `feed_device` take the window of compressed bytes that starts at
+    `position` and return the StreamResult of the feed: `consumed` bytes of the window were decoded to `out_len` bytes;
+    `consumed == 0` with `need_comp` asks for a longer window.  S3S_E_CAPACITY is NOT raised (the stream stays usable):
+    the result carries `need_dst` and `.code == E_CAPACITY`.  Every other error raises CodecError and sticks.
+    `close()` raises E_BAD_FRAME when the range was not read to its end.  Also a context manager (which closes quietly after
+    an exception, loudly otherwise)."""
+
+    def __init__(self, codec_ctx: Codec, codec: int, checksum: int, part_offsets, ref_checksums=None):
+        self._ctx = codec_ctx
+        self._lib = codec_ctx._lib
+        offs = _i64(part_offsets)
+        refs = _i64(ref_checksums) if ref_checksums is not None else None
+        h = ctypes.c_void_p(None)
+        self._s = None
+        rc = self._lib.s3s_dstream_open(codec_ctx._h, codec, checksum, _p64(offs), _p64(refs) if refs is not None else None,
+                                        len(offs) - 1, ctypes.byref(h))
+        codec_ctx._check(rc)
+        self._s = h.value
+
+    @property
+    def position(self) -> int:
+        return int(self._lib.s3s_dstream_position(self._s))
+
+    def _feed(self, fn, comp_ptr, comp_len, dst_ptr, dst_capacity):
+        if not self._s:
+            raise ValueError("the stream is closed")
+        r = StreamResult()
+        rc = fn(self._s, comp_ptr, int(comp_len), dst_ptr, int(dst_capacity), ctypes.byref(r))
+        r.code = int(rc)
+        if rc != 0 and rc != E_CAPACITY:
+            self._ctx._check(rc, r.bad_partition)
+        return r
+
+    def feed(self, comp: np.ndarray, dst: np.ndarray, dst_capacity: Optional[int] = None) -> StreamResult:
+        """Host buffers: `comp` is the window (uint8), the decoded bytes land in dst[:result.out_len]."""
+        comp = np.ascontiguousarray(comp, dtype=np.uint8)
+        if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable):
+            raise ValueError("dst must be a writable C-contiguous uint8 array (the library writes into it)")
+        cap = dst.size if dst_capacity is None else int(dst_capacity)
+        if not 0 <= cap <= dst.size:
+            raise ValueError(f"dst_capacity {cap} is outside dst's {dst.size} bytes")
+        return self._feed(self._lib.s3s_dstream_feed, comp.ctypes.data if comp.size else None, comp.size,
+                          dst.ctypes.data if cap else None, cap)
+
+    def feed_device(self, d_comp: int, comp_len: int, d_dst: int, dst_capacity: int) -> StreamResult:
+        """Device pointers on the context's device."""
+        return self._feed(self._lib.s3s_dstream_feed_device, ctypes.c_void_p(d_comp) if comp_len else None, comp_len,
+                          ctypes.c_void_p(d_dst) if dst_capacity else None, dst_capacity)
+
+    def close(self, check: bool = True) -> int:
+        """Frees the stream; returns the code s3s_dstream_close gave (raises it when `check` and it is not S3S_OK)."""
+        if not self._s:
+            return 0
+        rc = int(self._lib.s3s_dstream_close(self._s))
+        self._s = None
+        if check and rc != 0:
+            raise CodecError(rc, "the stream was closed before the end of the range" if rc == E_BAD_FRAME else "the stream had failed")
+        return rc
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *exc):
+        self.close(check=exc_type is None)
+
+    def __del__(self):
+        try:
+            if self._s and getattr(self._ctx, "_h", None):
+                self.close(check=False)
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
 
 
 class PinnedBuffer:
