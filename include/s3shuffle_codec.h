@@ -413,6 +413,14 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          NOTE: the one-shot call reports a wrong checksum before a corrupt frame.  A feed does so for the partitions whose
  *          last byte its window holds; a corrupt frame in a partition that is still open is reported first, as
  *          S3S_E_BAD_FRAME, by the feed that meets it.
+ *          That holds for a corrupt header and for a corrupt payload alike.
+ * Size     need_dst never exceeds 32 MiB (1 << 25, lz4-java's largest block and the largest unit any decoder here takes).  An
+ *          LZ4Block header is bounded by its level nibble and an LZF chunk by its 16-bit field; a Snappy chunk whose varint
+ *          claims more is refused by the feed that meets it: S3S_E_UNSUPPORTED, consumed = 0, out_len = 0, need_dst = 0 -
+ *          never S3S_E_CAPACITY, which would send the caller for a buffer of up to 4 GiB - 1 on the word of one flipped bit.
+ *          (With checksums on, a wrong checksum of a partition whose last byte the window holds is still reported first.)
+ *          The refusal does not fail the stream - nothing was consumed, the same feed gets the same answer - and
+ *          s3s_dstream_close then says the range was not read to its end.
  * Errors   stick: after S3S_E_CHECKSUM or S3S_E_BAD_FRAME every later feed returns the same code (and bad_partition).
  * Result   the concatenation of all dst outputs is what s3s_decompress_range_device writes for the same range, and the final
  *          verdict falls in the same class.

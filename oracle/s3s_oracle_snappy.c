@@ -296,12 +296,15 @@ int64_t s3o_snappy_decompress_stream(const uint8_t* src, int64_t clen, uint8_t* 
     if (got < 0) {
       /* distinguish capacity from corruption: peek the varint */
       uint32_t ulen = 0;
-      int sh = 0;
+      int sh = 0, whole = 0; /* whole: the varint ends inside the chunk and within five bytes - else it is corruption */
       for (uint32_t i = 0; i < c && sh <= 28; i++, sh += 7) {
         ulen |= (uint32_t)(src[ip + i] & 0x7f) << sh;
-        if (!(src[ip + i] & 0x80)) break;
+        if (!(src[ip + i] & 0x80)) {
+          whole = 1;
+          break;
+        }
       }
-      return (int64_t)ulen > room ? S3O_E_CAPACITY : S3O_E_BAD_FRAME;
+      return whole && (int64_t)ulen > room ? S3O_E_CAPACITY : S3O_E_BAD_FRAME;
     }
     ip += c;
     op += got;

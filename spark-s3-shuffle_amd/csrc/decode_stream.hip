@@ -192,12 +192,23 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   }
   // the one-shot call reports a wrong checksum before a corrupt frame: so does a feed for the partitions whose last byte its
   // window holds (a corrupt frame in a partition that is still open comes first - nothing else is known about it yet)
-  auto corrupt = [&](const char* what) -> int {
+  auto wrong_sum = [&]() -> int32_t {  // the first partition whose last byte the window holds and whose checksum is wrong, or -1
     if (do_sum)
       for (int32_t i = 0; i < n; i++)
-        if (s->off[(size_t)(s->cur + i) + 1] <= wend && h_sums[i] != s->ref[(size_t)(s->cur + i)])
-          return stick(s, r, S3S_E_CHECKSUM, s->cur + i, "");
-    return stick(s, r, S3S_E_BAD_FRAME, -1, what);
+        if (s->off[(size_t)(s->cur + i) + 1] <= wend && h_sums[i] != s->ref[(size_t)(s->cur + i)]) return s->cur + i;
+    return -1;
+  };
+  auto corrupt = [&](const char* what) -> int {
+    const int32_t bad = wrong_sum();
+    return bad >= 0 ? stick(s, r, S3S_E_CHECKSUM, bad, "") : stick(s, r, S3S_E_BAD_FRAME, -1, what);
+  };
+  // discovery's status word: a unit that claims more decoded bytes than any decoder takes is refused, not corrupt - nothing is
+  // consumed, need_dst stays 0 (never S3S_E_CAPACITY: the caller would be sent for up to 4 GiB), and the same feed gets the
+  // same answer.  A wrong checksum of a partition whose last byte the window holds still comes first.
+  auto refused = [&](int32_t st, const char* what) -> int {
+    if (st != S3S_E_UNSUPPORTED) return corrupt(what);
+    const int32_t bad = wrong_sum();
+    return bad >= 0 ? stick(s, r, S3S_E_CHECKSUM, bad, "") : fail(ctx, S3S_E_UNSUPPORTED, "codec block larger than the decoder takes");
   };
 
   // ---- discovery: the whole units of the window, then the cut at dst_capacity -----------------------------------------------
@@ -233,7 +244,8 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     HIP_TRY(ctx, hipMemcpyAsync(&h_misc[1], d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&h_misc[2], d_result, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (*reinterpret_cast<int32_t*>(&h_misc[1]) != 0) return corrupt(codec == S3S_CODEC_LZ4 ? "frame chain" : "chunk chain");
+    if (*reinterpret_cast<int32_t*>(&h_misc[1]) != 0)
+      return refused(*reinterpret_cast<int32_t*>(&h_misc[1]), codec == S3S_CODEC_LZ4 ? "frame chain" : "chunk chain");
     n_frames = h_misc[0];
     const int64_t stop = h_misc[2];
     need_comp = h_misc[3];
@@ -260,7 +272,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
       HIP_TRY(ctx, hipMemcpyAsync(&h_misc[1], d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(ctx, hipMemcpyAsync(&h_misc[2], d_result, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      if (*reinterpret_cast<int32_t*>(&h_misc[1]) != 0) return corrupt("frame header");
+      if (*reinterpret_cast<int32_t*>(&h_misc[1]) != 0) return refused(*reinterpret_cast<int32_t*>(&h_misc[1]), "frame header");
       k = h_misc[2];
       consumed = h_misc[3];
       out_len = h_misc[4];
@@ -331,7 +343,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
       st = *reinterpret_cast<int32_t*>(&h_misc[1]);
     }
     if (st == S3S_E_UNSUPPORTED) return fail(ctx, S3S_E_UNSUPPORTED, "codec block larger than the decoder takes");
-    if (st != 0) return stick(s, r, S3S_E_BAD_FRAME, -1, "frame payload");
+    if (st != 0) return corrupt("frame payload");  // (the capacity cut may have left a partition's end, which the window holds, unconsumed)
     if (second) carry = h_sums[n];
   }
 

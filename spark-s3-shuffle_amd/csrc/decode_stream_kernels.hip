@@ -137,6 +137,9 @@ __global__ __launch_bounds__(256) void frames_cut_kernel(const Frame* __restrict
 // pend is the one-shot walk's corruption (-1), one that fits there but not in front of `end` ends the walk: *stop = where
 // it starts, *need = its length as far as the piece shows it (the header's when the header is cut, then header + payload).
 // mid: the piece starts inside a Snappy stream, so no stream header is expected at beg.  Returns the chunks in front of *stop.
+// A Snappy chunk whose varint claims more than kBatchMaxBlock decoded bytes ends the walk with -2: no decoder takes it, and a
+// caller must not be sent for a buffer of that size (need_dst) - an LZ4Block frame is bounded by parse_header, an LZF chunk by
+// its 16-bit field, a Snappy varint by nothing.
 struct PieceWalk {
   int64_t ip, end, pend, need;
   // 0: x more bytes are there; 1: the window ends first (need set); -1: the partition ends first
@@ -200,6 +203,7 @@ __device__ int walk_piece_stream(const uint8_t* comp, int64_t beg, int64_t end, 
         ulen |= (b & 0x7fu) << sh;
         if (!(b & 0x80u)) break;
       }
+      if (ulen > (uint32_t)kBatchMaxBlock) return -2;
       f = Frame{w.ip + 4, (int32_t)cl, (int32_t)ulen, 0u, 1};
     }
     if (emit) {
@@ -214,6 +218,13 @@ __device__ int walk_piece_stream(const uint8_t* comp, int64_t beg, int64_t end, 
   return n;
 }
 
+// One lane per piece raises the window's status word, so the word must not depend on which lane comes last: corruption in any
+// piece (-1) is S3S_E_BAD_FRAME whatever the other pieces say, a refused claim (-2) is written only over "no error".
+__device__ __forceinline__ void raise_piece_status(int32_t* status, int n) {
+  if (n == -2) atomicCAS(status, 0, S3S_E_UNSUPPORTED);
+  else atomicExch(status, S3S_E_BAD_FRAME);
+}
+
 // result (written for the LAST piece, the only one a window can cut): [0] = stop offset, [1] = need
 __global__ void snappy_count_stream_kernel(const uint8_t* __restrict__ comp, const int64_t* __restrict__ piece_off, int32_t n_pieces,
                                            int32_t first_mid, int64_t last_pend, uint32_t* __restrict__ piece_nframes,
@@ -224,7 +235,7 @@ __global__ void snappy_count_stream_kernel(const uint8_t* __restrict__ comp, con
   int64_t stop = end, need = 0;
   const int n = walk_piece_stream(comp, piece_off[p], end, p == n_pieces - 1 ? last_pend : end, p == 0 && first_mid != 0, chunk_format,
                                   false, nullptr, nullptr, &stop, &need);
-  if (n < 0) atomicExch(status, S3S_E_BAD_FRAME);
+  if (n < 0) raise_piece_status(status, n);
   piece_nframes[p] = n < 0 ? 0u : (uint32_t)n;
   if (p == n_pieces - 1) {
     result[0] = stop;
@@ -240,9 +251,9 @@ __global__ void snappy_emit_stream_kernel(const uint8_t* __restrict__ comp, cons
   if (p >= n_pieces) return;
   const int64_t end = piece_off[p + 1], b = frame_base[p];
   int64_t stop, need;
-  if (walk_piece_stream(comp, piece_off[p], end, p == n_pieces - 1 ? last_pend : end, p == 0 && first_mid != 0, chunk_format, true,
-                        frames + b, frame_orig + b, &stop, &need) < 0)
-    atomicExch(status, S3S_E_BAD_FRAME);
+  const int n = walk_piece_stream(comp, piece_off[p], end, p == n_pieces - 1 ? last_pend : end, p == 0 && first_mid != 0, chunk_format,
+                                  true, frames + b, frame_orig + b, &stop, &need);
+  if (n < 0) raise_piece_status(status, n);
 }
 
 // A checksum continued (s3s_checksum_ranges_seeded*, the carried state of s3s_dstream_feed*): the seed is the checksum of

@@ -476,7 +476,9 @@ class DecodeStream:
     """One s3s_dstream: the streaming reduce side.  `feed` / `feed_device` take the window of compressed bytes that starts at
     `position` and return the StreamResult of the feed: `consumed` bytes of the window were decoded to `out_len` bytes;
     `consumed == 0` with `need_comp` asks for a longer window.  S3S_E_CAPACITY is NOT raised (the stream stays usable):
-    the result carries `need_dst` and `.code == E_CAPACITY`.  Every other error raises CodecError and sticks.
+    the result carries `need_dst` and `.code == E_CAPACITY`.  Every other error raises CodecError; E_BAD_FRAME and E_CHECKSUM
+    stick, E_UNSUPPORTED from a feed (a unit that claims more than any decoder takes) consumes nothing and repeats.
+    `last_result` is the StreamResult of the latest feed, also of one that raised.
     `close()` raises E_BAD_FRAME when the range was not read to its end.  Also a context manager (which closes quietly after
     an exception, loudly otherwise)."""
 
@@ -487,6 +489,7 @@ class DecodeStream:
         refs = _i64(ref_checksums) if ref_checksums is not None else None
         h = ctypes.c_void_p(None)
         self._s = None
+        self.last_result = None
         rc = self._lib.s3s_dstream_open(codec_ctx._h, codec, checksum, _p64(offs), _p64(refs) if refs is not None else None,
                                         len(offs) - 1, ctypes.byref(h))
         codec_ctx._check(rc)
@@ -502,6 +505,7 @@ class DecodeStream:
         r = StreamResult()
         rc = fn(self._s, comp_ptr, int(comp_len), dst_ptr, int(dst_capacity), ctypes.byref(r))
         r.code = int(rc)
+        self.last_result = r
         if rc != 0 and rc != E_CAPACITY:
             self._ctx._check(rc, r.bad_partition)
         return r

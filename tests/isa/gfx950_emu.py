@@ -1627,6 +1627,22 @@ class Program:
             if ret:
                 w.v[i.ops[0][1]][lane] = old
 
+    def x_global_atomic_cmpswap(self, w, i):
+        # global_atomic_cmpswap [vdst,] vaddr, vdata[2], saddr: vdata = the new value, vdata + 1 = the value compared — as x_global_atomic_add
+        ret = len(i.ops) == 4
+        vaddr, vdata, saddr = (i.ops[1], i.ops[2], i.ops[3]) if ret else (i.ops[0], i.ops[1], i.ops[2])
+        addrs = self._gaddr(w, i, vaddr, saddr)
+        for lane in np.flatnonzero(w.em()):
+            one = np.zeros(64, dtype=bool)
+            one[lane] = True
+            old = w.mem.load(addrs, one, 4).view("<u4")[lane, 0]
+            if int(old) == int(w.v[vdata[1] + 1][lane]):
+                new = np.zeros((64, 4), dtype=np.uint8)
+                new[lane] = np.array([int(w.v[vdata[1]][lane]) & 0xFFFFFFFF], dtype="<u4").view(np.uint8)
+                w.mem.store(addrs, one, new)
+            if ret:
+                w.v[i.ops[0][1]][lane] = old
+
     def x_global_atomic_xor(self, w, i):
         # global_atomic_xor [vdst,] vaddr, vdata, saddr — as x_global_atomic_add
         ret = len(i.ops) == 4
