@@ -428,12 +428,40 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          stream follows from it) and no device memory between feeds: a feed works in the context's workspace, and other
  *          calls on the same context may run between two feeds.  The context stays single-threaded and must outlive the
  *          stream.  s3s_dstream_feed (host buffers) stages the window and dst_capacity bytes of output in that workspace:
- *          the caller's two sizes are the memory bound.
+ *          the caller's two sizes are the memory bound.  (A stream opened by s3s_dstream_open_encrypted holds one more
+ *          window-sized buffer there during a feed: the decrypted window.)
  * Refused  at open with S3S_E_UNSUPPORTED, context intact: S3S_CODEC_ZSTD (a frame is a whole partition with history across
- *          its blocks and, from zstd-jni's streaming writer, no content size: resumable Zstandard is separate work) and any
- *          context with IO encryption on (the key stream would have to be sought mid-partition).  Both keep the one-shot
- *          call.  S3S_OPT_LZ4_DECODE_VARIANT = 3 WORKS: a feed launches whichever decoder the option names.
- * Not here a streaming map side, a reader in the C++ host mirror, a batched feed of several streams. */
+ *          its blocks and, from zstd-jni's streaming writer, no content size: resumable Zstandard is separate work) and, by
+ *          s3s_dstream_open, any context with IO encryption on: callers from before s3s_dstream_open_encrypted rely on that
+ *          answer to fall back, and the units of an encrypted range are new to a caller (below) - s3s_dstream_open_encrypted
+ *          is the opt-in.  Both keep the one-shot call.  S3S_OPT_LZ4_DECODE_VARIANT = 3 WORKS: a feed launches whichever
+ *          decoder the option names.
+ * Not here a streaming map side, a reader in the C++ host mirror, a batched feed of several streams.
+ *
+ * Under Spark IO encryption: s3s_dstream_open_encrypted (ABI 11, additive: callers detect support by the symbol) takes the
+ * arguments of s3s_dstream_open and makes its checks, requires the layer to be on (off: S3S_E_INVALID) and refuses
+ * S3S_CODEC_ZSTD alike.  part_offsets index the STORED bytes, IVs included; so do the window, consumed, need_comp and the
+ * position.  CTR is seekable - key stream block j is AES_K(IV + j) - so a window may start anywhere in a partition's cipher
+ * text.  The contract above holds with these changes only:
+ * IV unit  the 16-byte IV of a non-empty partition is a unit.  It decodes to no bytes, so it always fits dst_capacity.  It is
+ *          consumed only when all 16 bytes are in the window: a window that starts at a partition's start and shows fewer than
+ *          16 bytes gets S3S_OK, consumed = 0, need_comp = 16.  The position is therefore never inside an IV.
+ * Units    every other unit is the codec's unit of the plain stream; its stored position is the plain position plus the IVs in
+ *          front of it.  need_comp, need_dst, the capacity cut, the 32 MiB bound on need_dst and the Snappy oversized-claim
+ *          refusal keep their meaning; need_comp takes one more step at most (the IV).
+ * Short    a partition of exactly 16 stored bytes is an empty stream.  One of 1 .. 15 stored bytes is S3S_E_BAD_FRAME, sticky,
+ *          from the feed that would consume into it (it has taken everything in front and its window shows a byte of it); a
+ *          wrong checksum of a partition whose last byte the window holds is still reported first.
+ * Checksum over the stored bytes; timing, verdicts and stickiness unchanged.
+ * Key      the stream is bound to the key setting it was opened under: after any later successful s3s_set_io_encryption on
+ *          the context, on or off, the same key or another, its feeds answer S3S_E_INVALID and it can only be closed (a call
+ *          refused for its key length changes nothing, here too).  No key material is
+ *          copied into the stream.
+ * State    still host-only: it additionally holds the open partition's IV (16 bytes, wiped at close); where its key stream
+ *          stands follows from the position.  Between feeds the stream holds no device memory; one-shot encrypted calls on the
+ *          same context may run between two feeds.
+ * Result   the concatenation of all dst outputs is what s3s_decompress_range_device writes for the same range under the same
+ *          key, and the final verdict falls in the same class. */
 typedef struct s3s_dstream s3s_dstream;
 typedef struct s3s_dstream_result {
   int64_t consumed;      /* bytes of this window taken; the next window starts there */
@@ -448,6 +476,8 @@ typedef struct s3s_dstream_result {
  * every entry point this one returns the code; the stream comes back through *out (NULL on failure). */
 int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
                      int32_t nparts, s3s_dstream** out);
+int s3s_dstream_open_encrypted(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
+                               int32_t nparts, s3s_dstream** out);
 int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_len, uint8_t* d_dst, int64_t dst_capacity,
                             s3s_dstream_result* r);
 int s3s_dstream_feed(s3s_dstream* s, const uint8_t* comp, int64_t comp_len, uint8_t* dst, int64_t dst_capacity, /* host buffers */

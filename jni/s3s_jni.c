@@ -338,23 +338,39 @@ extern int64_t s3s_dstream_position(const s3s_dstream* s) __attribute__((weak));
 extern int s3s_dstream_close(s3s_dstream* s) __attribute__((weak));
 extern int s3s_checksum_ranges_seeded(s3s_ctx* ctx, int checksum_algo, const uint8_t* data, const int64_t* offsets, int32_t n,
                                       const int64_t* seeds, int64_t* out) __attribute__((weak));
+/* a range stored under IO encryption (offsets, windows and positions count the stored bytes, IVs included).  WEAK on its own:
+ * a library that has the streams but not this entry point answers S3S_E_UNSUPPORTED, and the caller keeps the JVM stack. */
+extern int s3s_dstream_open_encrypted(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
+                                      int32_t nparts, s3s_dstream** out) __attribute__((weak));
 #define STREAM(s) ((s3s_dstream*)(intptr_t)(s))
 
-JNIEXPORT jint JNICALL FN(dstreamOpen)(JNIEnv* e, jclass c, jlong h, jint codec, jint algo, jlongArray partOffsets,
-                                       jlongArray refChecksums, jint nparts, jlongArray outStream) {
-  (void)c;
-  if (!s3s_dstream_open) return S3S_E_UNSUPPORTED;
+typedef int (*dstream_open_fn)(s3s_ctx*, int, int, const int64_t*, const int64_t*, int32_t, s3s_dstream**);
+
+/* dstreamOpen and dstreamOpenEncrypted: the same arguments, the same checks */
+static jint dstream_open(JNIEnv* e, dstream_open_fn open, jlong h, jint codec, jint algo, jlongArray partOffsets, jlongArray refChecksums,
+                         jint nparts, jlongArray outStream) {
+  if (!open) return S3S_E_UNSUPPORTED;
   if (!outStream || (*e)->GetArrayLength(e, outStream) < 1) return S3S_E_INVALID;
   if (partOffsets && (*e)->GetArrayLength(e, partOffsets) < nparts + 1) return S3S_E_INVALID; /* (the library reads nparts + 1 / nparts entries) */
   if (refChecksums && (*e)->GetArrayLength(e, refChecksums) < nparts) return S3S_E_INVALID;
   jlong *po = pin(e, partOffsets), *rs = pin(e, refChecksums), *os = pin(e, outStream);
   s3s_dstream* s = NULL;
-  const int rc = s3s_dstream_open(CTX(h), codec, algo, (const int64_t*)po, (const int64_t*)rs, nparts, &s);
+  const int rc = open(CTX(h), codec, algo, (const int64_t*)po, (const int64_t*)rs, nparts, &s);
   os[0] = (jlong)(intptr_t)s;
   unpin(e, partOffsets, po, JNI_ABORT);
   unpin(e, refChecksums, rs, JNI_ABORT);
   unpin(e, outStream, os, 0);
   return rc;
+}
+JNIEXPORT jint JNICALL FN(dstreamOpen)(JNIEnv* e, jclass c, jlong h, jint codec, jint algo, jlongArray partOffsets,
+                                       jlongArray refChecksums, jint nparts, jlongArray outStream) {
+  (void)c;
+  return dstream_open(e, s3s_dstream_open, h, codec, algo, partOffsets, refChecksums, nparts, outStream);
+}
+JNIEXPORT jint JNICALL FN(dstreamOpenEncrypted)(JNIEnv* e, jclass c, jlong h, jint codec, jint algo, jlongArray partOffsets,
+                                                jlongArray refChecksums, jint nparts, jlongArray outStream) {
+  (void)c;
+  return dstream_open(e, s3s_dstream_open_encrypted, h, codec, algo, partOffsets, refChecksums, nparts, outStream);
 }
 JNIEXPORT jint JNICALL FN(dstreamFeed)(JNIEnv* e, jclass c, jlong stream, jobject comp, jlong compOff, jlong compLen,
                                        jobject dst, jlong dstCap, jlongArray out) {

@@ -153,8 +153,11 @@ object S3GpuStreams {
 //
 // Threading: the library context belongs to the task thread (S3SCodec.forThread); read() runs on the thread that opened the
 // stream - the task thread that iterates the block, as with the reference's streams.
-// Out of scope here: Zstandard ranges and ranges under IO encryption (dstreamOpen answers E_UNSUPPORTED: the caller keeps
-// the JVM stack), a streaming map side, a batched feed of several streams.
+// IO encryption: with a key set on the context (OPT_IO_ENCRYPTION_KEY_BITS > 0) the range is opened by dstreamOpenEncrypted:
+// offsets, windows and positions count the stored bytes, a partition's 16-byte IV is a unit of its own that decodes to
+// nothing, and a window that shows less than a whole IV gets need_comp = 16 - an ordinary "fetch more" to this reader.
+// Out of scope here: Zstandard ranges (the open answers E_UNSUPPORTED: the caller keeps the JVM stack), a streaming map
+// side, a batched feed of several streams.
 object S3GpuStreamingInputStream {
   /** spark.shuffle.s3.gpu.streamWindowBytes: the size of the compressed and of the decoded buffer of one stream.  A feed costs
     * ~0.5 ms whatever it holds, so the default is the largest window measured: 64 MiB (profiles/decode_stream.md, host-64m:
@@ -165,12 +168,16 @@ object S3GpuStreamingInputStream {
     math.min(math.max(SparkEnv.get.conf.getSizeAsBytes("spark.shuffle.s3.gpu.streamWindowBytes", DefaultWindowBytes), 64L << 10),
              S3GpuBuffers.MaxBuffer)
 
-  /** None: the library cannot stream this range (E_UNSUPPORTED: no stream entry points, Zstandard, IO encryption) - the caller
-    * takes the JVM stack over `source`, which is untouched.  `firstPartition` is r0 of the range (exception messages). */
+  /** None: the library cannot stream this range (E_UNSUPPORTED: no stream entry points, Zstandard, or a key on a library from
+    * before dstreamOpenEncrypted) - the caller takes the JVM stack over `source`, which is untouched.  `firstPartition` is r0 of
+    * the range (exception messages). */
   def open(blockName: String, source: InputStream, rangeLength: Long, ctx: Long, codec: Int, algo: Int, rel: Array[Long],
            refs: Array[Long], firstPartition: Int): Option[S3GpuStreamingInputStream] = {
     val handle = new Array[Long](1)
-    val rc = S3SCodec.dstreamOpen(ctx, codec, algo, rel, refs, rel.length - 1, handle)
+    val encrypted = S3SCodec.getOption(ctx, S3SCodec.OPT_IO_ENCRYPTION_KEY_BITS) > 0 // (E_INVALID, negative: a library without the layer)
+    val rc =
+      if (encrypted) S3SCodec.dstreamOpenEncrypted(ctx, codec, algo, rel, refs, rel.length - 1, handle)
+      else S3SCodec.dstreamOpen(ctx, codec, algo, rel, refs, rel.length - 1, handle)
     if (rc == S3SCodec.E_UNSUPPORTED) None
     else {
       S3SCodec.check(ctx, rc, blockName)

@@ -79,9 +79,15 @@ object S3SCodec {
   // streaming reduce side (s3s_dstream_*: a range of any size decoded window by window, S3GpuStreamingInputStream) and the
   // seeded checksums under it.  A stream is a Long; the window is comp[compOff, compOff + compLen) of a direct buffer;
   // out = { consumed, out_len, need_comp, need_dst, bad_partition, at_end }.  E_UNSUPPORTED: a library from before the streams,
-  // a Zstandard range, or a context with IO encryption on - the caller keeps the JVM path.
+  // a Zstandard range, or dstreamOpen on a context with IO encryption on - the caller keeps the JVM path.
+  // dstreamOpenEncrypted is the open for a context with a key set (off: E_INVALID): partOffsets, the windows and the position
+  // count the STORED bytes, IVs included; a partition's IV is a 16-byte unit that decodes to nothing (need_comp = 16 when the
+  // window shows less of it), and the stream is bound to the key setting it was opened under.  E_UNSUPPORTED: a library from
+  // before this entry point.
   @native def dstreamOpen(handle: Long, codec: Int, algo: Int, partOffsets: Array[Long], refChecksums: Array[Long],
                           nparts: Int, outStream: Array[Long]): Int
+  @native def dstreamOpenEncrypted(handle: Long, codec: Int, algo: Int, partOffsets: Array[Long], refChecksums: Array[Long],
+                                   nparts: Int, outStream: Array[Long]): Int
   @native def dstreamFeed(stream: Long, comp: ByteBuffer, compOff: Long, compLen: Long, dst: ByteBuffer, dstCap: Long,
                           out: Array[Long]): Int
   @native def dstreamPosition(stream: Long): Long

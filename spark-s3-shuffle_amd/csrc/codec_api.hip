@@ -213,6 +213,7 @@ int s3s_set_io_encryption(s3s_ctx* ctx, const uint8_t* key, int32_t key_bytes) {
   if (!key || key_bytes == 0) {  // off: nothing of the key stays behind
     wipe(&ctx->enc_keys, sizeof ctx->enc_keys);
     ctx->enc_rounds = ctx->enc_key_bits = 0;
+    ctx->enc_epoch++;
     return S3S_OK;
   }
   if (key_bytes != 16 && key_bytes != 24 && key_bytes != 32)  // (the message names the length, never a key byte)
@@ -223,6 +224,7 @@ int s3s_set_io_encryption(s3s_ctx* ctx, const uint8_t* key, int32_t key_bytes) {
   wipe(&fresh, sizeof fresh);
   ctx->enc_rounds = rounds;
   ctx->enc_key_bits = 8 * key_bytes;
+  ctx->enc_epoch++;
   return S3S_OK;
 }
 

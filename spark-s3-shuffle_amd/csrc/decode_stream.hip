@@ -10,8 +10,18 @@
 // Host waits per feed, as in s3s_decompress_range_device: discovery, frame table + cut, decode.  The checksums of the
 // window's pieces of partitions are queued in front of discovery and arrive with its first wait; only the piece of a partition
 // that the CUT leaves open (the capacity ended the feed inside it) is summed again, behind the decode launch.
+//
+// Under Spark IO encryption (s3s_dstream_open_encrypted) a feed has two sides.  The STORED side - the window as fetched, IVs
+// included - is what the checksums run over and what consumed, need_comp and the position count.  The PLAIN side is the window
+// decrypted into the crypt workspace by the window form of the AES-CTR pass (aes_ctr_stream.hip), queued in front of
+// discovery: discovery, the emit kernels, the cut and the decoders read it with plain offsets and do not know of the layer.
+// The host maps a plain offset back by adding 16 for every IV passed.  No wait is added: the IVs that start in the window
+// come back with the first wait, and the one of the partition a feed leaves open stays in the stream (host memory).
+#include <algorithm>
 #include <new>
 
+#define S3S_AES_DEVICE
+#include "aes_ctr_core.h"
 #include "s3s_ctx.h"
 
 using namespace s3s;
@@ -26,6 +36,12 @@ struct s3s_dstream {
   int64_t carry = 0;              // checksum state of partition cur over [off[cur], pos)
   int err = S3S_OK;               // sticky: S3S_E_CHECKSUM / S3S_E_BAD_FRAME
   int32_t bad_partition = -1;
+  // s3s_dstream_open_encrypted: pos and off are STORED coordinates.  pos is never inside an IV: it is off[cur] (the IV of
+  // partition cur not consumed yet) or at least off[cur] + 16, and then iv holds that IV
+  bool enc = false;
+  uint64_t epoch = 0;         // the context's key setting the stream is bound to (s3s_ctx::enc_epoch)
+  std::vector<int64_t> poff;  // plain offsets of the partitions: a stored partition of 16 bytes or more loses its IV, a shorter one is empty
+  uint8_t iv[16] = {};
 };
 
 namespace {
@@ -36,9 +52,11 @@ inline bool at_end(const s3s_dstream* s) { return s->pos == s->off[(size_t)s->np
 
 // the smallest window that can hold a unit's header when the window shows nothing of it
 inline int64_t min_unit(const s3s_dstream* s) {
+  const int64_t part_start = s->off[(size_t)(s->cur < s->nparts ? s->cur : s->nparts)];
+  if (s->enc && s->pos == part_start) return s3s_aes::kBlock;  // the IV is the next unit
   switch (s->codec) {
     case S3S_CODEC_LZ4: return kLz4FrameHeader;
-    case S3S_CODEC_SNAPPY: return s->pos == s->off[(size_t)(s->cur < s->nparts ? s->cur : s->nparts)] ? kSnappyStreamHeader : 4;
+    case S3S_CODEC_SNAPPY: return s->pos == part_start + (s->enc ? s3s_aes::kBlock : 0) ? kSnappyStreamHeader : 4;
     case S3S_CODEC_LZF: return 5;
     default: return 1;
   }
@@ -53,12 +71,29 @@ int stick(s3s_dstream* s, s3s_dstream_result* r, int code, int32_t bad_partition
   return fail(s->ctx, code, "Stream is corrupted (%s, range offset %lld)", what, (long long)s->pos);
 }
 
-}  // namespace
+// S3S_CODEC_NONE under encryption: the stored bytes of the window [pos, pos + len) that a feed takes when dst holds cap bytes.
+// Known before anything runs: a unit is a byte, or an IV (no output) that is whole in the window.  A window that shows a cut
+// IV or a partition shorter than one is left whole - the feed itself decides on those, and its plain bytes fit cap.
+int64_t none_cut_encrypted(const s3s_dstream* s, int64_t len, int64_t cap) {
+  const int64_t wend = s->pos + len;
+  int64_t out = 0;
+  for (int32_t p = s->cur; p < s->nparts && s->off[(size_t)p] < wend; p++) {
+    const int64_t a = s->off[(size_t)p], b = s->off[(size_t)p + 1];
+    if (b == a) continue;
+    int64_t c = s->pos;  // the first cipher byte of the partition in the window: the open partition's is the position
+    if (s->pos <= a) {
+      if (b - a < s3s_aes::kBlock || a + s3s_aes::kBlock > wend) return len;
+      c = a + s3s_aes::kBlock;
+    }
+    const int64_t e = b < wend ? b : wend;
+    if (e - c > cap - out) return c + (cap - out) - s->pos;
+    out += e - c;
+  }
+  return len;
+}
 
-extern "C" {
-
-int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
-                     int32_t nparts, s3s_dstream** out) {
+int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums, int32_t nparts,
+                s3s_dstream** out, bool encrypted) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   if (!out) return fail(ctx, S3S_E_INVALID, "null/invalid argument");
@@ -74,10 +109,11 @@ int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* 
     if (part_offsets[p + 1] < part_offsets[p]) return fail(ctx, S3S_E_INVALID, "part_offsets not monotonic at %d", p);
   if (checksum_algo != S3S_CHECKSUM_NONE && nparts > 0 && !ref_checksums)
     return fail(ctx, S3S_E_INVALID, "ref_checksums is null but a checksum algorithm is selected");
+  if (encrypted && !enc_on(ctx)) return fail(ctx, S3S_E_INVALID, "s3s_dstream_open_encrypted on a context without IO encryption");
   if (codec == S3S_CODEC_ZSTD)  // a frame is a whole partition with history across its blocks: no unit to stop at
     return fail(ctx, S3S_E_UNSUPPORTED, "Zstandard ranges cannot be streamed (use s3s_decompress_range*)");
-  if (enc_on(ctx))  // the key stream would have to be sought to the middle of a partition
-    return fail(ctx, S3S_E_UNSUPPORTED, "ranges under IO encryption cannot be streamed (use s3s_decompress_range*)");
+  if (!encrypted && enc_on(ctx))  // the caller has to know the IV unit: s3s_dstream_open_encrypted is the opt-in
+    return fail(ctx, S3S_E_UNSUPPORTED, "ranges under IO encryption are streamed by s3s_dstream_open_encrypted");
   s3s_dstream* s = new (std::nothrow) s3s_dstream();
   if (!s) return fail(ctx, S3S_E_NOMEM, "out of host memory");
   s->ctx = ctx;
@@ -87,8 +123,31 @@ int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* 
   s->off.assign(part_offsets, part_offsets + nparts + 1);
   if (checksum_algo != S3S_CHECKSUM_NONE && nparts > 0) s->ref.assign(ref_checksums, ref_checksums + nparts);
   s->carry = fresh(checksum_algo);
+  if (encrypted) {
+    s->enc = true;
+    s->epoch = ctx->enc_epoch;
+    s->poff.assign((size_t)nparts + 1, 0);
+    for (int32_t p = 0; p < nparts; p++) {
+      const int64_t len = part_offsets[p + 1] - part_offsets[p];
+      s->poff[(size_t)p + 1] = s->poff[(size_t)p] + (len >= s3s_aes::kBlock ? len - s3s_aes::kBlock : 0);
+    }
+  }
   *out = s;
   return S3S_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
+                     int32_t nparts, s3s_dstream** out) {
+  return open_stream(ctx, codec, checksum_algo, part_offsets, ref_checksums, nparts, out, false);
+}
+
+int s3s_dstream_open_encrypted(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
+                               int32_t nparts, s3s_dstream** out) {
+  return open_stream(ctx, codec, checksum_algo, part_offsets, ref_checksums, nparts, out, true);
 }
 
 int64_t s3s_dstream_position(const s3s_dstream* s) { return s ? s->pos : (int64_t)S3S_E_INVALID; }
@@ -96,6 +155,7 @@ int64_t s3s_dstream_position(const s3s_dstream* s) { return s ? s->pos : (int64_
 int s3s_dstream_close(s3s_dstream* s) {
   if (!s) return S3S_E_INVALID;
   const int rc = s->err != S3S_OK ? s->err : at_end(s) ? S3S_OK : S3S_E_BAD_FRAME;
+  wipe(s->iv, sizeof s->iv);
   delete s;
   return rc;
 }
@@ -116,7 +176,10 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   if (comp_len < 0 || dst_capacity < 0 || (comp_len > 0 && !d_comp) || (dst_capacity > 0 && !d_dst))
     return fail(ctx, S3S_E_INVALID, "null/invalid argument");
   if (comp_len > left) return fail(ctx, S3S_E_INVALID, "the window reaches %lld bytes past the end of the range", (long long)(comp_len - left));
-  if (enc_on(ctx)) return fail(ctx, S3S_E_UNSUPPORTED, "IO encryption was switched on after the stream was opened");
+  const bool enc = s->enc;
+  if (enc && (s->epoch != ctx->enc_epoch || !enc_on(ctx)))  // bound to the key setting it was opened under: it can only be closed
+    return fail(ctx, S3S_E_INVALID, "s3s_set_io_encryption was called on the context after the stream was opened");
+  if (!enc && enc_on(ctx)) return fail(ctx, S3S_E_UNSUPPORTED, "IO encryption was switched on after the stream was opened");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (auto& v : ctx->stage_ms) v = 0;
   const bool do_sum = s->algo != S3S_CHECKSUM_NONE;
@@ -124,7 +187,8 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
 
   // bytes this feed looks at: S3S_CODEC_NONE's units are bytes, so its cut is known before anything runs
   int64_t L = comp_len;
-  if (codec == S3S_CODEC_NONE && dst_capacity < L) L = dst_capacity;
+  if (codec == S3S_CODEC_NONE && !enc && dst_capacity < L) L = dst_capacity;
+  if (codec == S3S_CODEC_NONE && enc) L = none_cut_encrypted(s, comp_len, dst_capacity);  // (0: the next unit is a byte and dst holds none)
   if (comp_len > 0 && L == 0) {
     r->need_dst = 1;
     return fail(ctx, S3S_E_CAPACITY, "dst_capacity 0 < 1");
@@ -149,7 +213,9 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
   const size_t n1 = (size_t)n + 1;
   const size_t o_off2 = al(8 * n1), o_seg = al(o_off2 + 16), o_seg2 = al(o_seg + 4 * n1), o_seed = al(o_seg2 + 8),
-               o_sums = al(o_seed + 8 * n1), o_misc = al(o_sums + 8 * n1), stage_total = o_misc + 64;
+               o_sums = al(o_seed + 8 * n1), o_misc = al(o_sums + 8 * n1),
+               // encrypted: [plain piece offsets n + 1][first cipher byte of every piece n + 1][the IVs that start in the window n + 1]
+               o_q = al(o_misc + 64), o_c = al(o_q + 8 * n1), o_iv = al(o_c + 8 * n1), stage_total = enc ? o_iv + 16 * n1 : o_misc + 64;
   int rc;
   if ((rc = ensure_stage(ctx, stage_total))) return rc;
   uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
@@ -160,6 +226,9 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   int64_t* h_seed = reinterpret_cast<int64_t*>(hs + o_seed);
   int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);  // [n] = the second launch's sum
   int64_t* h_misc = reinterpret_cast<int64_t*>(hs + o_misc);  // [0] n_frames, [1] status, [2..5] stop, need / k, consumed, out_len, need
+  int64_t* h_q = reinterpret_cast<int64_t*>(hs + o_q);
+  int64_t* h_c = reinterpret_cast<int64_t*>(hs + o_c);
+  const uint8_t* h_iv = hs + o_iv;
   int64_t segs = 0;
   for (int32_t i = 0; i < n; i++) {
     const int64_t a = s->off[(size_t)(s->cur + i)] - s->pos, b = s->off[(size_t)(s->cur + i) + 1] - s->pos;
@@ -173,16 +242,83 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   h_seg[n] = (int32_t)segs;
   if (segs > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "window too large for one feed");
   const int64_t last_pend = n > 0 ? s->off[(size_t)(s->cur + n)] - s->pos : 0;  // where the last piece's partition ends (>= L: the window cuts it)
+  // ---- the plain side: what discovery and the decoders see.  Without the layer it IS the stored side ----------------------
+  // Encrypted: the first m pieces, up to the first whose IV the window's end cuts (iv_cut: it contributes nothing yet) or
+  // whose partition is shorter than an IV (short_part: corrupt, reported by the feed that consumes everything in front of it)
+  const int64_t front = enc && s->cur < np ? s->pos - s->off[(size_t)s->cur] : 0;  // stored bytes of partition cur in front of the window: 0 or >= 16
+  const int64_t pfront = front > 0 ? front - s3s_aes::kBlock : 0;                  // ... and plain ones
+  int32_t m = n;
+  int64_t PL = L;
+  bool iv_cut = false, short_part = false;
+  if (enc) {
+    m = 0;
+    PL = 0;
+    for (int32_t i = 0; i < n; i++) {
+      const int64_t stored = s->off[(size_t)(s->cur + i) + 1] - s->off[(size_t)(s->cur + i)];
+      int64_t c;
+      if (i == 0 && front > 0) c = 0;
+      else if (stored == 0) c = h_off[i];
+      else if (stored < s3s_aes::kBlock) { short_part = true; break; }
+      else if (h_off[i + 1] - h_off[i] < s3s_aes::kBlock) { iv_cut = true; break; }
+      else c = h_off[i] + s3s_aes::kBlock;
+      h_q[i] = PL;
+      h_c[i] = c;
+      PL += h_off[i + 1] - c;
+      m = i + 1;
+    }
+    h_q[m] = PL;
+  }
+  // a plain offset of the window as a stored one: add 16 for every IV passed (an IV in front of the next plain byte is passed:
+  // a unit of no output always fits)
+  auto to_stored = [&](int64_t x) -> int64_t {
+    if (!enc) return x;    // one coordinate system
+    if (m == 0) return 0;  // no plain piece (a cut IV or a short partition at the window's start): nothing can be consumed
+    // the LAST piece that starts at or in front of x (h_q[0] = 0 <= x): of several pieces that start AT x - empty ones, and the
+    // one x lies in - the last, so that the IVs (and empty partitions) between them are passed
+    const int64_t i = (std::upper_bound(h_q, h_q + m, x) - h_q) - 1;
+    return h_c[i] + (x - h_q[i]);
+  };
+  const int32_t pn = m;
+  // piece 0 starts inside a codec stream (no Snappy stream header expected there): plain bytes of its partition lie in front
+  const bool first_mid = enc ? pfront > 0 : s->pos > s->off[(size_t)s->cur];
+  // what the RANGE still holds from the window's start, in plain bytes: a unit that crosses it is corrupt, not cut
+  int64_t pleft = left;
+  if (enc && short_part) pleft = PL;  // the plain side ends at a partition shorter than its IV: nothing valid lies behind it
+  else if (enc) pleft = s->poff[(size_t)np] - (s->poff[(size_t)s->cur] + pfront);
+  // where the last plain piece's partition ends, window-relative in plain bytes (>= PL when the window cuts it)
+  int64_t plast_pend = last_pend;
+  if (enc && m == 0) plast_pend = 0;  // no plain piece at all
+  else if (enc) {
+    const int64_t plain_len = s->poff[(size_t)(s->cur + m)] - s->poff[(size_t)(s->cur + m) - 1];  // of partition cur + m - 1
+    plast_pend = h_q[m - 1] + plain_len - (m == 1 ? pfront : 0);  // (m == 1: it is the open partition, pfront of it lie in front)
+  }
   // device: B_OFFSETS [piece offsets n + 1][2], B_REF_SUMS [seeds n + 1], B_SUMS [n + 1], B_STATUS [status][pad][result 4 x int64]
   if ((rc = ensure(ctx, B_OFFSETS, 8 * (n1 + 2)))) return rc;
   if ((rc = ensure(ctx, B_REF_SUMS, 8 * n1))) return rc;
   if ((rc = ensure(ctx, B_SUMS, 8 * n1))) return rc;
   if ((rc = ensure(ctx, B_STATUS, 64))) return rc;
   int64_t* d_off = dev<int64_t>(ctx, B_OFFSETS);
+  const uint8_t* P = d_comp;      // the plain bytes of the window
+  const int64_t* d_poff = d_off;  // ... and their pieces
+  if (enc) {  // device: B_CRYPT [the window decrypted], B_CRYPT_OFF [plain piece offsets n + 1][IVs n + 1]
+    if ((rc = ensure(ctx, B_CRYPT, (size_t)PL + 64))) return rc;
+    if ((rc = ensure(ctx, B_CRYPT_OFF, 24 * n1))) return rc;
+    d_off = dev<int64_t>(ctx, B_OFFSETS);
+    P = dev<uint8_t>(ctx, B_CRYPT);
+    d_poff = dev<int64_t>(ctx, B_CRYPT_OFF);
+  }
   int32_t* d_status = dev<int32_t>(ctx, B_STATUS);
   int64_t* d_result = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_STATUS) + 16);
   HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, 64, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_off, h_off, 8 * n1, hipMemcpyHostToDevice, ctx->stream));
+  if (enc && m > 0 && h_off[m] > 0) {  // the decrypt pass, in front of discovery; the IVs it gathers arrive with the first wait
+    uint8_t* d_iv = dev<uint8_t>(ctx, B_CRYPT_OFF) + 8 * n1;
+    const AesWindowIv iv0 = {{s3s_aes::load_be32(s->iv), s3s_aes::load_be32(s->iv + 4), s3s_aes::load_be32(s->iv + 8), s3s_aes::load_be32(s->iv + 12)}};
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_CRYPT_OFF].p, h_q, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, ctx->stream));
+    launch_aes_ctr_window(ctx->enc_keys, ctx->enc_rounds, iv0, d_comp, dev<uint8_t>(ctx, B_CRYPT), d_off, d_poff, d_iv, m, front, h_off[m], ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(hs + o_iv, d_iv, 16 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+  }
   if (do_sum && n > 0) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_REF_SUMS].p, h_seed, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = run_checksum(ctx, s->algo, d_comp, d_off, n, h_seg, dev<int64_t>(ctx, B_SUMS), L))) return rc;
@@ -212,12 +348,13 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   };
 
   // ---- discovery: the whole units of the window, then the cut at dst_capacity -----------------------------------------------
-  int64_t n_frames = 0, k = 0, consumed = L, out_len = L, need_comp = 0;
-  if (codec == S3S_CODEC_NONE) {
+  // (consumed and need_comp are plain offsets here; they are mapped back behind the cut)
+  int64_t n_frames = 0, k = 0, consumed = PL, out_len = PL, need_comp = 0;
+  if (codec == S3S_CODEC_NONE || PL == 0) {  // (no plain byte: the window holds IVs, whole or cut, and nothing else)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   } else {
     const int cf = codec == S3S_CODEC_LZF ? kChunkLzf : kChunkSnappy;
-    const int32_t n_tiles = codec == S3S_CODEC_LZ4 ? lz4_tile_count(L) : 0;
+    const int32_t n_tiles = codec == S3S_CODEC_LZ4 ? lz4_tile_count(PL) : 0;
     int64_t *d_true_entry = nullptr, *d_base = nullptr;
     if (codec == S3S_CODEC_LZ4) {
       const size_t tile_i64 = sizeof(int64_t) * (size_t)(n_tiles + 1);
@@ -227,7 +364,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
       d_true_entry = d_spec_exit + (n_tiles + 1);
       d_base = d_true_entry + (n_tiles + 1);
       int32_t* d_spec_count = reinterpret_cast<int32_t*>(d_base + (n_tiles + 1));
-      launch_lz4_discover_stream(d_comp, L, left, n_tiles, d_spec_entry, d_spec_exit, d_spec_count, d_true_entry, d_base, d_status,
+      launch_lz4_discover_stream(P, PL, pleft, n_tiles, d_spec_entry, d_spec_exit, d_spec_count, d_true_entry, d_base, d_status,
                                  d_result, ctx->stream);
       HIP_TRY(ctx, hipMemcpyAsync(&h_misc[0], d_base + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     } else {
@@ -235,10 +372,9 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
       if ((rc = ensure(ctx, B_PART_NFRAMES, cnt_bytes + sizeof(int64_t) * (n1 + 1)))) return rc;
       uint32_t* d_cnt = dev<uint32_t>(ctx, B_PART_NFRAMES);
       d_base = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_PART_NFRAMES) + cnt_bytes);
-      launch_snappy_count_frames_stream(d_comp, d_off, n, s->pos > s->off[(size_t)s->cur], last_pend, d_cnt, d_status, d_result,
-                                        ctx->stream, cf);
-      launch_scan_u32(d_cnt, n, d_base, ctx->stream);
-      HIP_TRY(ctx, hipMemcpyAsync(&h_misc[0], d_base + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+      launch_snappy_count_frames_stream(P, d_poff, pn, first_mid, plast_pend, d_cnt, d_status, d_result, ctx->stream, cf);
+      launch_scan_u32(d_cnt, pn, d_base, ctx->stream);
+      HIP_TRY(ctx, hipMemcpyAsync(&h_misc[0], d_base + pn, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(&h_misc[1], d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -249,7 +385,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     n_frames = h_misc[0];
     const int64_t stop = h_misc[2];
     need_comp = h_misc[3];
-    if (stop < 0 || stop > L || (stop < L && need_comp <= L - stop)) return fail(ctx, S3S_E_HIP, "frame discovery returned an impossible stop offset");
+    if (stop < 0 || stop > PL || (stop < PL && need_comp <= PL - stop)) return fail(ctx, S3S_E_HIP, "frame discovery returned an impossible stop offset");
     if (n_frames > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "too many frames in one feed");
     k = 0;
     consumed = stop;
@@ -259,10 +395,10 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
       if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_frames + 1)))) return rc;
       if ((rc = ensure(ctx, B_FRAME_OUT, sizeof(int64_t) * (size_t)(n_frames + 1)))) return rc;
       if (codec == S3S_CODEC_LZ4) {  // the one-shot emit, with the stop offset as the end of the bytes: the chain ends exactly there
-        launch_lz4_emit_frames(d_comp, stop, lz4_tile_count(stop), d_true_entry, d_base, dev<Frame>(ctx, B_FRAMES),
+        launch_lz4_emit_frames(P, stop, lz4_tile_count(stop), d_true_entry, d_base, dev<Frame>(ctx, B_FRAMES),
                                dev<uint32_t>(ctx, B_ITEM_SIZE), n_frames, dev<int64_t>(ctx, B_FRAME_OUT), d_status, ctx->stream);
       } else {
-        launch_snappy_emit_frames_stream(d_comp, d_off, n, s->pos > s->off[(size_t)s->cur], last_pend, d_base, dev<Frame>(ctx, B_FRAMES),
+        launch_snappy_emit_frames_stream(P, d_poff, pn, first_mid, plast_pend, d_base, dev<Frame>(ctx, B_FRAMES),
                                          dev<uint32_t>(ctx, B_ITEM_SIZE), d_status, ctx->stream, cf);
         launch_scan_u32(dev<uint32_t>(ctx, B_ITEM_SIZE), n_frames, dev<int64_t>(ctx, B_FRAME_OUT), ctx->stream);
       }
@@ -278,11 +414,17 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
       out_len = h_misc[4];
       if (k < 0 || k > n_frames || consumed < 0 || consumed > stop || out_len < 0 || out_len > dst_capacity)
         return fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible frame index");
-      if (consumed == 0) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
+      if (consumed == 0 && to_stored(0) == 0) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
         r->need_dst = h_misc[5];
         return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld decoded bytes of the next unit", (long long)dst_capacity, (long long)h_misc[5]);
       }
     }
+  }
+
+  if (enc) {  // back to the stored side
+    if (short_part && consumed == PL) return corrupt("partition shorter than its IV");  // this feed would consume into it
+    consumed = to_stored(consumed);
+    if (consumed == 0 && iv_cut) need_comp = s3s_aes::kBlock;  // the window starts with a partition and shows less than its IV
   }
 
   // ---- the verdict of every partition whose last byte this feed consumes, before anything is decoded ---------------------
@@ -310,15 +452,15 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
 
   // ---- decode the cut frame table with the one-shot path's decoders ----------------------------------------------------------
   if (codec == S3S_CODEC_NONE) {
-    HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_comp, (size_t)consumed, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_dst, P, (size_t)out_len, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   } else if (k > 0 || second) {
     if (k > 0) {
       if (codec == S3S_CODEC_LZ4)
-        launch_lz4_decompress(d_comp, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status,
+        launch_lz4_decompress(P, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status,
                               ctx->lz4_decode_variant, ctx->stream);
       else
-        launch_snappy_decompress(d_comp, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status,
+        launch_snappy_decompress(P, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status,
                                  ctx->lz4_decode_variant, ctx->stream, codec == S3S_CODEC_LZF ? kChunkLzf : kChunkSnappy);
       HIP_TRY(ctx, hipGetLastError());
     }
@@ -336,7 +478,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     int32_t st = *reinterpret_cast<int32_t*>(&h_misc[1]);
     if (st == S3S_E_UNSUPPORTED && codec == S3S_CODEC_LZ4 && ctx->lz4_decode_variant != 3) {  // a frame above 32 MiB: the ring decoder, as in the one-shot call
       HIP_TRY(ctx, hipMemsetAsync(d_status, 0, 16, ctx->stream));
-      launch_lz4_decompress(d_comp, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status, 3, ctx->stream);
+      launch_lz4_decompress(P, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status, 3, ctx->stream);
       HIP_TRY(ctx, hipGetLastError());
       HIP_TRY(ctx, hipMemcpyAsync(&h_misc[1], d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -347,6 +489,8 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     if (second) carry = h_sums[n];
   }
 
+  if (enc && q < np && new_pos > s->off[(size_t)q] && !(q == s->cur && front > 0))  // the open partition's IV: it started in this window
+    memcpy(s->iv, h_iv + 16 * (size_t)(q - s->cur), sizeof s->iv);
   s->pos = new_pos;
   s->cur = q;
   s->carry = carry;

@@ -78,6 +78,7 @@ struct s3s_ctx {
   // to the AES-CTR kernel as arguments; they are wiped when the layer is switched off and in s3s_destroy
   s3s::AesKeys enc_keys = {};
   int enc_rounds = 0, enc_key_bits = 0;
+  uint64_t enc_epoch = 0;           // counts the s3s_set_io_encryption calls that took effect: an encrypted s3s_dstream is bound to the one it was opened under
   bool enc_suspended = false;       // reduce side: the wrapped call on the decrypted bytes runs with the layer off
   std::vector<uint8_t> ivs;         // s3s_set_stream_ivs: the IVs of the NEXT compress call (consumed by it, success or not)
   bool ivs_set = false;

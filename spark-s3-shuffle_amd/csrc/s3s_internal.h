@@ -122,6 +122,18 @@ int64_t aes_ctr_max_bytes();
 void launch_aes_ctr(int mode, const AesKeys& keys, int rounds, const uint8_t* d_in, uint8_t* d_out, const int64_t* d_stored_off,
                     const int64_t* d_plain_off, const uint8_t* d_ivs, int32_t n_parts, int64_t stored_bound, int64_t stored_limit,
                     hipStream_t st);
+// The window form (aes_ctr_stream.hip; the arithmetic is aes_ctr_stream_core.h): the stored window d_in[0, window_len) of a
+// streamed range -> its plain bytes, IVs dropped.  d_stored_off[n_pieces + 1] are the window's pieces of partitions (window-
+// relative, [0] = 0, [n_pieces] = window_len; every piece but the first starts with its partition, and an IV is whole in the
+// window or its piece is empty), d_plain_off[n_pieces + 1] where their plain bytes go in d_out.  `front` stored bytes of piece
+// 0's partition lie in front of the window: 0, or >= 16 and iv0 is that partition's IV (four big-endian words).  The IV of
+// every piece that starts with one is copied to d_iv_out[16 piece ..].
+struct AesWindowIv {
+  uint32_t w[4];
+};
+void launch_aes_ctr_window(const AesKeys& keys, int rounds, const AesWindowIv& iv0, const uint8_t* d_in, uint8_t* d_out,
+                           const int64_t* d_stored_off, const int64_t* d_plain_off, uint8_t* d_iv_out, int32_t n_pieces, int64_t front,
+                           int64_t window_len, hipStream_t st);
 // item_size = 16 for every kItemIv record (between the codec kernels and the scan)
 void launch_seed_iv_items(const Item* d_items, int32_t n_items, uint32_t* d_item_size, hipStream_t st);
 // exclusive scan of item sizes + partition index extraction

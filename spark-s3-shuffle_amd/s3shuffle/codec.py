@@ -161,6 +161,8 @@ def load_library() -> ctypes.CDLL:
         lib.s3s_dstream_position.restype = ctypes.c_int64
         lib.s3s_dstream_position.argtypes = [vp]
         lib.s3s_dstream_close.argtypes = [vp]
+    if hasattr(lib, "s3s_dstream_open_encrypted"):  # streams under IO encryption (additive, detected by the symbol)
+        lib.s3s_dstream_open_encrypted.argtypes = lib.s3s_dstream_open.argtypes
     _LIB = lib
     return lib
 
@@ -388,9 +390,10 @@ class Codec:
         return out[:n]
 
     # ---- reduce side ---------------------------------------------------------------------------
-    def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None) -> "DecodeStream":
-        """A fetched range decoded window by window in bounded memory (s3s_dstream_*)."""
-        return DecodeStream(self, codec, checksum, part_offsets, ref_checksums)
+    def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False) -> "DecodeStream":
+        """A fetched range decoded window by window in bounded memory (s3s_dstream_*); `encrypted`: a range stored under IO
+        encryption, through s3s_dstream_open_encrypted (offsets, windows and positions count the stored bytes, IVs included)."""
+        return DecodeStream(self, codec, checksum, part_offsets, ref_checksums, encrypted=encrypted)
 
     def decompressed_size(self, codec: int, comp: np.ndarray) -> int:
         comp = np.ascontiguousarray(comp, dtype=np.uint8)
@@ -480,9 +483,11 @@ class DecodeStream:
     stick, E_UNSUPPORTED from a feed (a unit that claims more than any decoder takes) consumes nothing and repeats.
     `last_result` is the StreamResult of the latest feed, also of one that raised.
     `close()` raises E_BAD_FRAME when the range was not read to its end.  Also a context manager (which closes quietly after
-    an exception, loudly otherwise)."""
+    an exception, loudly otherwise).
+    `encrypted=True` opens the stream with s3s_dstream_open_encrypted (the context's IO encryption must be on): a partition's
+    16-byte IV is a unit of its own that decodes to nothing, and the stream is bound to the key setting it was opened under."""
 
-    def __init__(self, codec_ctx: Codec, codec: int, checksum: int, part_offsets, ref_checksums=None):
+    def __init__(self, codec_ctx: Codec, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False):
         self._ctx = codec_ctx
         self._lib = codec_ctx._lib
         offs = _i64(part_offsets)
@@ -490,8 +495,10 @@ class DecodeStream:
         h = ctypes.c_void_p(None)
         self._s = None
         self.last_result = None
-        rc = self._lib.s3s_dstream_open(codec_ctx._h, codec, checksum, _p64(offs), _p64(refs) if refs is not None else None,
-                                        len(offs) - 1, ctypes.byref(h))
+        if encrypted and not hasattr(self._lib, "s3s_dstream_open_encrypted"):
+            raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_dstream_open_encrypted")
+        fn = self._lib.s3s_dstream_open_encrypted if encrypted else self._lib.s3s_dstream_open
+        rc = fn(codec_ctx._h, codec, checksum, _p64(offs), _p64(refs) if refs is not None else None, len(offs) - 1, ctypes.byref(h))
         codec_ctx._check(rc)
         self._s = h.value
 

@@ -12,6 +12,9 @@ the whole range
                 4 MiB compressed each (what a caller can do today where the partitions are small)
   host-64m / -16m   s3s_dstream_feed on page-locked host buffers, the shape of the Scala stream: ONE compressed and ONE
                 decoded buffer of that size, so the capacity ends most feeds; upload, decode and download of a feed do not overlap
+  enc-one-shot / enc-stream-whole / enc-stream-16m / -4m / enc-host-64m   the same range stored under IO encryption (AES-128,
+                written by this library's map side): the one-shot encrypted call and s3s_dstream_open_encrypted with the inputs
+                and windows of the rows above, in the same process - against the plain rows, the layer's cost per feed
 
 Times are a host clock around calls that end in a stream synchronise; every figure is the median of --steps calls after
 --warmup, with the fastest and slowest beside it.  The comparison is between the rows, never against a target.
@@ -108,6 +111,67 @@ def gpu_step(name, args):
         cap = min(8 * window, decoded)
         feeds = stream(window, cap, check=True)
         row(mode, timed(lambda: stream(window, cap), args.steps, args.warmup), feeds)
+
+    # the same range stored under IO encryption (AES-128): the one-shot encrypted call, then s3s_dstream_open_encrypted with the
+    # windows above, in the same process as the plain legs - the difference is the layer's cost per feed
+    if hasattr(c._lib, "s3s_dstream_open_encrypted"):
+        c.set_io_encryption(bytes(range(16)))
+        try:
+            c.set_stream_ivs(np.random.default_rng(11).integers(0, 256, 16 * (len(offs) - 1), dtype=np.uint8))
+            e_img, e_index, e_sums = c.compress_map_output(codec, CRC, data, offs)
+            e_total = int(e_index[-1])
+            d_enc = torch.from_numpy(np.ascontiguousarray(e_img)).to(dev)
+            torch.cuda.synchronize()
+
+            def enc_one_shot():
+                assert c.decompress_range_device(codec, CRC, d_enc.data_ptr(), e_total, e_index, e_sums, d_out.data_ptr(), decoded) == decoded
+
+            def enc_stream(window, cap, check=False):
+                feeds, n_out = 0, 0
+                with s3shuffle.DecodeStream(c, codec, CRC, e_index, e_sums, encrypted=True) as s:
+                    while True:
+                        pos = s.position
+                        r = s.feed_device(d_enc.data_ptr() + pos, min(window, e_total - pos), d_out.data_ptr(), cap)
+                        assert r.code == 0 and (r.consumed > 0 or r.at_end), (r.code, pos, r.need_comp, r.need_dst)
+                        if check and r.out_len:
+                            assert np.array_equal(d_out[:r.out_len].cpu().numpy(), want[n_out:n_out + r.out_len]), "encrypted stream output differs"
+                        feeds, n_out = feeds + 1, n_out + r.out_len
+                        if r.at_end:
+                            break
+                assert n_out == decoded
+                return feeds
+
+            enc_one_shot()
+            assert np.array_equal(d_out[:decoded].cpu().numpy(), want), "one-shot encrypted decode differs from the source"
+            row("enc-one-shot", timed(enc_one_shot, args.steps, args.warmup))
+            feeds = enc_stream(e_total, decoded, check=True)
+            row("enc-stream-whole", timed(lambda: enc_stream(e_total, decoded), args.steps, args.warmup), feeds)
+            for mode, window in WINDOWS[1:]:
+                cap = min(8 * window, decoded)
+                feeds = enc_stream(window, cap, check=True)
+                row("enc-" + mode, timed(lambda: enc_stream(window, cap), args.steps, args.warmup), feeds)
+            h_comp, h_out = s3shuffle.PinnedBuffer(e_total), s3shuffle.PinnedBuffer(64 << 20)
+            h_comp.array[:e_total] = e_img
+
+            def enc_host_stream():
+                feeds, n_out = 0, 0
+                with s3shuffle.DecodeStream(c, codec, CRC, e_index, e_sums, encrypted=True) as s:
+                    while True:
+                        pos = s.position
+                        r = s.feed(h_comp.array[pos:min(pos + (64 << 20), e_total)], h_out.array)
+                        assert r.code == 0 and (r.consumed > 0 or r.at_end), (r.code, pos, r.need_comp, r.need_dst)
+                        feeds, n_out = feeds + 1, n_out + r.out_len
+                        if r.at_end:
+                            break
+                assert n_out == decoded
+                return feeds
+
+            feeds = enc_host_stream()
+            row("enc-host-64m", timed(enc_host_stream, max(args.steps // 2, 1), 1), feeds)
+            h_comp.free()
+            h_out.free()
+        finally:
+            c.set_io_encryption(None)
 
     # sub-ranges of whole partitions, at most 4 MiB compressed each, one one-shot call per sub-range
     subs, r0 = [], 0
