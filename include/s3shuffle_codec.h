@@ -180,9 +180,17 @@ enum {
                                     'Z' 'V' 0 | len | bytes of LZFOutputStream, a pure function of the source bytes, the offsets
                                     and the options; compress-lzf's LZFInputStream, liblzf and this library decode it;
                                     s3s_max_compressed_size* answer ulen + 7 x ceil(ulen / 65535) per segment */
-  S3S_OPT_IO_ENCRYPTION_KEY_BITS = 11 /* ABI 11, additive, READ-ONLY: 0 (the layer is off), 128, 192 or 256 - the key that
+  S3S_OPT_IO_ENCRYPTION_KEY_BITS = 11, /* ABI 11, additive, READ-ONLY: 0 (the layer is off), 128, 192 or 256 - the key that
                                     s3s_set_io_encryption holds.  s3s_set_option on it answers S3S_E_INVALID; a library without
                                     the layer answers S3S_E_INVALID to s3s_get_option too, which is how callers detect it */
+  S3S_OPT_STREAM_CLASS = 12      /* ABI 11, additive, READ-ONLY: the hardware-queue pool of the context's stream.  The runtime keeps
+                                    one pool of GPU_MAX_HW_QUEUES queues (default 4) per stream priority and streams that share a
+                                    queue run one after the other, so s3s_create spreads the contexts of a device over the pools
+                                    by creation slot (the lowest free one; s3s_destroy returns it): 0 = lowest priority (the first
+                                    `cap` contexts), 1 = normal (the next cap-1), 2 = highest (the next cap-2), 3 = normal
+                                    priority beyond that, where contexts share queues.  S3S_STREAM_POOLS=0 in the environment
+                                    puts every stream at normal priority (answer 1); =2 fills normal, highest, lowest in that
+                                    order.  s3s_set_option on it answers S3S_E_INVALID */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */

@@ -9,6 +9,7 @@
 // every entry point needs a context.
 #include "s3s_ctx.h"
 #include <atomic>
+#include <mutex>
 
 using namespace s3s;
 
@@ -19,6 +20,53 @@ inline void dbg_sync(s3s_ctx* ctx, const char* what) {
   if (!on) return;
   const hipError_t e = hipStreamSynchronize(ctx->stream);
   fprintf(stderr, "[s3s] %s: %s\n", what, hipGetErrorString(e));
+}
+
+// Contexts alive on a device, one bit per slot.  A context takes the lowest free slot and the slot decides which of the
+// runtime's hardware-queue pools its stream goes to (stream_placement.h): without this every context is a normal-priority
+// stream, and with the default of 4 queues four task threads plus the application's own stream are five streams on four
+// queues - one context's uploads and pre-pass wait behind another context's whole codec kernel.
+struct StreamSlots {
+  std::mutex mu;
+  uint64_t used = 0;  // slots 0..63; contexts beyond that are not tracked (overflow class)
+};
+StreamSlots g_stream_slots[64];
+
+// the runtime's per-pool cap, as the runtime reads it (read only)
+int hw_queue_cap() {
+  const char* e = getenv("GPU_MAX_HW_QUEUES");
+  const int cap = e ? atoi(e) : 4;
+  return cap < 1 ? 1 : (cap > 32 ? 32 : cap);
+}
+
+hipError_t create_placed_stream(s3s_ctx* ctx) {
+  // S3S_STREAM_POOLS (A/B only): 0 = every stream at normal priority, 2 = normal pool first, then highest, then lowest
+  static const int order = getenv("S3S_STREAM_POOLS") ? atoi(getenv("S3S_STREAM_POOLS")) : 1;
+  int least = 0, greatest = 0;
+  if (order != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
+  const int levels = least - greatest + 1;
+  StreamSlots& S = g_stream_slots[ctx->device & 63];
+  {
+    std::lock_guard<std::mutex> g(S.mu);
+    for (int i = 0; i < 64; i++)
+      if (!(S.used >> i & 1)) {
+        S.used |= uint64_t(1) << i;
+        ctx->stream_slot = i;
+        break;
+      }
+  }
+  ctx->stream_class = stream_class_ordered(ctx->stream_slot >= 0 ? ctx->stream_slot : 64, hw_queue_cap(), levels, order);
+  if (ctx->stream_class == kStreamLowest) return hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, least);
+  if (ctx->stream_class == kStreamHighest) return hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, greatest);
+  return hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+}
+
+void release_stream_slot(s3s_ctx* ctx) {
+  if (ctx->stream_slot < 0) return;
+  StreamSlots& S = g_stream_slots[ctx->device & 63];
+  std::lock_guard<std::mutex> g(S.mu);
+  S.used &= ~(uint64_t(1) << ctx->stream_slot);
+  ctx->stream_slot = -1;
 }
 }  // namespace
 
@@ -49,6 +97,7 @@ s3s_ctx* s3s_create(int device_ordinal, int64_t scratch_bytes) {
   ctx->device = device_ordinal;
   auto bail = [&](const char* what, hipError_t err) -> s3s_ctx* {
     fail(nullptr, S3S_E_HIP, "%s failed: %s", what, hipGetErrorString(err));
+    release_stream_slot(ctx);
     delete ctx;
     return nullptr;
   };
@@ -57,8 +106,7 @@ s3s_ctx* s3s_create(int device_ordinal, int64_t scratch_bytes) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0) ctx->cu_count = cus;
   }
-  if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
-    return bail("hipStreamCreate", e);
+  if ((e = create_placed_stream(ctx)) != hipSuccess) return bail("hipStreamCreate", e);
   for (auto& ev : ctx->ev)
     if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
   if ((e = hipEventCreate(&ctx->ev_hash)) != hipSuccess) return bail("hipEventCreate", e);
@@ -113,6 +161,7 @@ void s3s_destroy(s3s_ctx* ctx) {
   if (ctx->hb_in && !ctx->hb_shared) hipStreamDestroy(ctx->hb_in);
   if (ctx->hb_out && !ctx->hb_shared) hipStreamDestroy(ctx->hb_out);
   if (ctx->stream) hipStreamDestroy(ctx->stream);
+  release_stream_slot(ctx);
   wipe(&ctx->enc_keys, sizeof ctx->enc_keys);
   delete ctx;
 }
@@ -185,6 +234,8 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
       return S3S_OK;
     case S3S_OPT_IO_ENCRYPTION_KEY_BITS:
       return fail(ctx, S3S_E_INVALID, "option %d is read-only (s3s_set_io_encryption switches the layer)", key);
+    case S3S_OPT_STREAM_CLASS:
+      return fail(ctx, S3S_E_INVALID, "option %d is read-only (the context's creation slot decides it)", key);
   }
   return fail(ctx, S3S_E_INVALID, "unknown option %d", key);
 }
@@ -203,6 +254,7 @@ int64_t s3s_get_option(const s3s_ctx* ctx, int key) {
     case S3S_OPT_ZSTD_COMPRESS: return ctx->zstd_compress;
     case S3S_OPT_LZF_COMPRESS: return ctx->lzf_compress;
     case S3S_OPT_IO_ENCRYPTION_KEY_BITS: return ctx->enc_key_bits;
+    case S3S_OPT_STREAM_CLASS: return ctx->stream_class;
   }
   return S3S_E_INVALID;
 }
@@ -688,23 +740,20 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
   }
   if (n_items64 > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "too many codec blocks in one call");
   const int32_t n_items = (int32_t)n_items64, n_chunks = (int32_t)n_chunks64;
-  const size_t np1 = (size_t)n_parts64 + (size_t)n_tasks;  // sum of (n_t + 1)
-  // pinned staging: [items][part_first (per task, relative)][seg_start (per task)][index out][sums out][status out]
-  const size_t items_bytes = sizeof(Item) * (size_t)n_items;
-  auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
-  const size_t o_items = 0, o_pf = al(o_items + items_bytes), o_seg = al(o_pf + 4 * np1), o_idx = al(o_seg + 4 * np1),
-               o_sums = al(o_idx + 8 * np1), o_status = al(o_sums + 8 * ((size_t)n_parts64 + 1)),
-               o_tails = al(o_status + 4 * (size_t)n_tasks + 16), stage_total = o_tails + sizeof(TaskTail) * (size_t)n_tasks + 16;
+  // one arena for the call's small arrays, laid out alike in the pinned staging block and on the device (PackedPlan)
+  const PackedPlan L = packed_plan((size_t)n_tasks, (size_t)n_parts64, (size_t)n_items, sizeof(TaskTail), sizeof(Item));
   int rc;
-  if ((rc = ensure_stage(ctx, stage_total))) return rc;
+  if ((rc = ensure_stage(ctx, L.total))) return rc;
   uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
-  Item* h_items = reinterpret_cast<Item*>(hs + o_items);
-  int32_t* h_pf = reinterpret_cast<int32_t*>(hs + o_pf);
-  int32_t* h_seg = reinterpret_cast<int32_t*>(hs + o_seg);
-  int64_t* h_idx = reinterpret_cast<int64_t*>(hs + o_idx);
-  int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);
-  int32_t* h_status = reinterpret_cast<int32_t*>(hs + o_status);
-  TaskTail* h_tails = reinterpret_cast<TaskTail*>(hs + o_tails);
+  Item* h_items = reinterpret_cast<Item*>(hs + L.items);
+  int32_t* h_pf = reinterpret_cast<int32_t*>(hs + L.part_first);
+  int32_t* h_seg = reinterpret_cast<int32_t*>(hs + L.seg_start);
+  int64_t* h_idx = reinterpret_cast<int64_t*>(hs + L.index);
+  int64_t* h_sums = reinterpret_cast<int64_t*>(hs + L.sums);
+  int32_t* h_status = reinterpret_cast<int32_t*>(hs + L.status);
+  TaskTail* h_tails = reinterpret_cast<TaskTail*>(hs + L.tails);
+  memset(hs + L.work, 0, 16);                            // the codec grid's block counter
+  memset(h_status, 0, L.up_end - L.status);              // the status words (the last call's download landed here)
   std::vector<int32_t> first_item((size_t)n_tasks + 1), first_part((size_t)n_tasks + 1), first_seg((size_t)n_tasks + 1);
   const uint8_t* base = tasks[0].d_src;  // item sources are offsets from one base pointer (signed 64-bit)
   {
@@ -755,19 +804,20 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
   }
   const int32_t total_segs = first_seg[(size_t)n_tasks];
   const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
-  if ((rc = ensure(ctx, B_ITEMS, items_bytes + 16))) return rc;
-  if ((rc = ensure(ctx, B_PART_FIRST, 4 * np1))) return rc;
-  if ((rc = ensure(ctx, B_SEG_START, 4 * np1))) return rc;
-  if ((rc = ensure(ctx, B_INDEX, 8 * np1))) return rc;
-  if ((rc = ensure(ctx, B_SUMS, 8 * ((size_t)n_parts64 + 1)))) return rc;
-  if ((rc = ensure(ctx, B_STATUS, 4 * (size_t)n_tasks + 16))) return rc;
+  if ((rc = ensure(ctx, B_PLAN, L.total))) return rc;
   if ((rc = ensure(ctx, B_PARTIAL, 16 * (size_t)(total_segs > 0 ? total_segs : 1)))) return rc;
   if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(n_chunks > 0 ? n_chunks : 1)))) return rc;
   if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
   if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * ((size_t)n_items + (size_t)n_tasks + 1)))) return rc;
   if ((rc = ensure(ctx, B_ITEM_CHECK, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
-  if ((rc = ensure(ctx, B_WORK, 64))) return rc;
-  if ((rc = ensure(ctx, B_TAILS, sizeof(TaskTail) * (size_t)n_tasks + 16))) return rc;
+  uint8_t* d_plan = dev<uint8_t>(ctx, B_PLAN);
+  const Item* d_items = reinterpret_cast<const Item*>(d_plan + L.items);
+  const TaskTail* d_tails = reinterpret_cast<const TaskTail*>(d_plan + L.tails);
+  const int32_t* d_pf = reinterpret_cast<const int32_t*>(d_plan + L.part_first);
+  const int32_t* d_seg = reinterpret_cast<const int32_t*>(d_plan + L.seg_start);
+  int32_t* d_status = reinterpret_cast<int32_t*>(d_plan + L.status);
+  int64_t* d_index = reinterpret_cast<int64_t*>(d_plan + L.index);
+  int64_t* d_sums = reinterpret_cast<int64_t*>(d_plan + L.sums);
   const int32_t zstd_grid = zstd_resident_groups(ctx, n_items);
   if (codec == S3S_CODEC_ZSTD && (rc = ensure(ctx, B_ZENC, (size_t)zstd_grid * (size_t)zstd_compress_scratch_stride()))) return rc;
   for (int32_t t = 0; t < n_tasks; t++) {  // what the once-per-call tail kernels need to know about each task
@@ -786,57 +836,50 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
     d.dst = k.d_dst;
     d.dst_capacity = k.dst_capacity;
   }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, 4 * (size_t)n_tasks + 16, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_TAILS].p, h_tails, sizeof(TaskTail) * (size_t)n_tasks, hipMemcpyHostToDevice, ctx->stream));
-  // one upload: items | part_first | seg_start are consecutive in the staging buffer but live in separate
-  // device buffers
-  if (n_items > 0)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_ITEMS].p, h_items, items_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_PART_FIRST].p, h_pf, 4 * np1, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_SEG_START].p, h_seg, 4 * np1, hipMemcpyHostToDevice, ctx->stream));
+  // ONE upload: block counter and status words (zeros), tails, items, part_first, seg_start
+  HIP_TRY(ctx, hipMemcpyAsync(d_plan, hs, L.up_end, hipMemcpyHostToDevice, ctx->stream));
   record(ctx, 0);
   // ---- ONE codec launch over every task's chunks ---------------------------------------------------------
   if (codec == S3S_CODEC_LZ4) {
     const int variant = ctx->lz4_variant == 9 ? 10 : ctx->lz4_variant;
     ctx->lz4_variant_used = variant;
-    launch_lz4_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint32_t>(ctx, B_ITEM_CHECK),
-                        dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<uint32_t>(ctx, B_WORK), lz4_resident_waves(ctx),
+    launch_lz4_compress(base, d_items, n_items, dev<uint32_t>(ctx, B_ITEM_CHECK),
+                        dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), reinterpret_cast<uint32_t*>(d_plan + L.work), lz4_resident_waves(ctx),
                         variant, ctx->stream,
-                        ctx->profile ? ctx->ev_hash : nullptr, bs >= kLz4U32From);
+                        ctx->profile ? ctx->ev_hash : nullptr, bs >= kLz4U32From, /*work_is_zero=*/true);
   } else if (codec == S3S_CODEC_ZSTD) {
-    launch_zstd_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
+    launch_zstd_compress(base, d_items, n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
                          dev<uint8_t>(ctx, B_ZENC), zstd_grid, ctx->stream);
   } else if (codec == S3S_CODEC_LZF) {
-    launch_lzf_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
+    launch_lzf_compress(base, d_items, n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
                         ctx->stream);
   } else {
-    launch_snappy_compress(base, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
+    launch_snappy_compress(base, d_items, n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
                            dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->snappy_variant, ctx->stream);
   }
   HIP_TRY(ctx, hipGetLastError());
   dbg_sync(ctx, "batch codec");
   record(ctx, 1);
   // ---- offsets, .data images, checksums of every task: one launch each (TaskTail, s3s_internal.h) ---------------------
-  launch_scan_items_batch(dev<TaskTail>(ctx, B_TAILS), n_tasks, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF),
-                          dev<int32_t>(ctx, B_PART_FIRST), dev<int64_t>(ctx, B_INDEX), ctx->stream);
+  launch_scan_items_batch(d_tails, n_tasks, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF),
+                          d_pf, d_index, ctx->stream);
   dbg_sync(ctx, "batch scan");
-  launch_gather_items_batch(dev<TaskTail>(ctx, B_TAILS), n_tasks, n_items, base, dev<Item>(ctx, B_ITEMS), dev<uint8_t>(ctx, B_SLOTS),
-                            slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF), dev<int32_t>(ctx, B_STATUS),
+  launch_gather_items_batch(d_tails, n_tasks, n_items, base, d_items, dev<uint8_t>(ctx, B_SLOTS),
+                            slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF), d_status,
                             ctx->stream);
   dbg_sync(ctx, "batch gather");
   HIP_TRY(ctx, hipGetLastError());
   record(ctx, 2);
   if (checksum_algo != S3S_CHECKSUM_NONE) {
-    launch_checksum_batch(checksum_algo, dev<TaskTail>(ctx, B_TAILS), n_tasks, total_segs, (int32_t)n_parts64, dev<int64_t>(ctx, B_INDEX),
-                          dev<int32_t>(ctx, B_SEG_START), ctx->buf[B_TABLES].p, dev<uint32_t>(ctx, B_PARTIAL), dev<int64_t>(ctx, B_SUMS),
+    launch_checksum_batch(checksum_algo, d_tails, n_tasks, total_segs, (int32_t)n_parts64, d_index,
+                          d_seg, ctx->buf[B_TABLES].p, dev<uint32_t>(ctx, B_PARTIAL), d_sums,
                           ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
   }
   record(ctx, 3);
-  HIP_TRY(ctx, hipMemcpyAsync(h_idx, ctx->buf[B_INDEX].p, 8 * np1, hipMemcpyDeviceToHost, ctx->stream));
-  if (checksum_algo != S3S_CHECKSUM_NONE && n_parts64 > 0)
-    HIP_TRY(ctx, hipMemcpyAsync(h_sums, ctx->buf[B_SUMS].p, 8 * (size_t)n_parts64, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(h_status, ctx->buf[B_STATUS].p, 4 * (size_t)n_tasks, hipMemcpyDeviceToHost, ctx->stream));
+  // ONE download: status | index | sums (without a checksum algorithm the sums are not read)
+  HIP_TRY(ctx, hipMemcpyAsync(h_status, d_status, (checksum_algo != S3S_CHECKSUM_NONE ? L.total : L.sums) - L.status, hipMemcpyDeviceToHost,
+                              ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->profile) {
     float ms = 0;

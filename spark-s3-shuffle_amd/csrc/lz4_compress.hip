@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(kWave) void xxh32_items_quad_kernel(
 
 void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                          uint32_t* d_item_check, uint8_t* d_slots, int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int resident_waves,
-                         int variant, hipStream_t st, hipEvent_t after_hash, bool has_u32) {
+                         int variant, hipStream_t st, hipEvent_t after_hash, bool has_u32, bool work_is_zero) {
   if (n_items <= 0) {
     if (after_hash) hipEventRecord(after_hash, st);
     return;
@@ -1093,8 +1093,8 @@ void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_it
     hipLaunchKernelGGL(xxh32_items_wave_kernel<kItemLz4ChunkU32>, dim3((unsigned)n_items), dim3(kWave), 0, st, d_src, d_items,
                        n_items, kLz4BlockSeed, d_item_check);
   if (after_hash) hipEventRecord(after_hash, st);
-  // d_work: the launch's block counter (zeroed in stream order); resident_waves: 10 per CU
-  (void)hipMemsetAsync(d_work, 0, sizeof(uint32_t), st);
+  // d_work: the launch's block counter (zeroed in stream order, here or by the caller's upload); resident_waves: 10 per CU
+  if (!work_is_zero) (void)hipMemsetAsync(d_work, 0, sizeof(uint32_t), st);
   static const int grid_env = getenv("S3S_LZ4_GRID") ? atoi(getenv("S3S_LZ4_GRID")) : 0;  // (experiments)
   int grid = grid_env > 0 ? grid_env : resident_waves;
   if (grid > n_items) grid = n_items;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "s3s_internal.h"
+#include "stream_placement.h"
 
 namespace s3s {
 
@@ -32,6 +33,7 @@ enum BufId {
   B_IVS,        // IO encryption, map side: one IV per partition of the call
   B_CRYPT,      // IO encryption, reduce side: the fetched range decrypted, IVs dropped
   B_CRYPT_OFF,  // IO encryption: stored / plain partition offsets of the AES-CTR pass where they are not B_INDEX
+  B_PLAN,  // batched map side: the call's small arrays in one arena, one upload and one download (PackedPlan, stream_placement.h)
   B_COUNT
 };
 
@@ -40,6 +42,8 @@ enum BufId {
 struct s3s_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  int stream_slot = -1;   // this context's slot in its device's registry (codec_api.hip), returned in s3s_destroy
+  int stream_class = 1;   // S3S_OPT_STREAM_CLASS: the queue pool the slot put the stream in (stream_placement.h)
   char err[512] = "";
   int64_t lz4_block = 32768;
   int64_t snappy_block = 32768;

@@ -88,9 +88,10 @@ constexpr uint32_t kRawFlag = 0x80000000u;
 //   slot_stride: bytes between slots (kSlotHeader + the block size rounded up to 16)
 //   has_u32: the items may hold kItemLz4ChunkU32 records (block size >= kLz4U32From): their hash pass and the byU32 parse
 //   are two more launches over the same items
+//   work_is_zero: *d_work is already zero in stream order (it travelled with the caller's upload): no memset is queued
 void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                          uint32_t* d_item_check, uint8_t* d_slots, int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int resident_waves,
-                         int variant, hipStream_t st, hipEvent_t after_hash = nullptr, bool has_u32 = false);
+                         int variant, hipStream_t st, hipEvent_t after_hash = nullptr, bool has_u32 = false, bool work_is_zero = false);
 // Snappy: same for kItemSnappyChunk.
 bool snappy_compress_available();
 //   slot_stride: bytes between slots (a raw snappy block can be larger than its chunk)

@@ -22,6 +22,7 @@ OPT_LZ4_BLOCK_SIZE_LARGE = 8  # ABI 10: spark.io.compression.lz4.blockSize 64 ..
 
 OPT_ZSTD_COMPRESS = 9  # ABI 11: 1 = write decode-compatible Zstandard frames on the map side (not libzstd's bytes); default 0
 OPT_LZF_COMPRESS = 10  # ABI 11, additive key: 1 = write decode-compatible LZF streams on the map side (not compress-lzf's bytes); default 0
+OPT_STREAM_CLASS = 12  # ABI 11, additive, read-only: queue pool of the context's stream (0 lowest priority, 1 normal, 2 highest, 3 shared)
 OPT_IO_ENCRYPTION_KEY_BITS = 11  # ABI 11, additive, read-only: 0 / 128 / 192 / 256 - the key Codec.set_io_encryption holds
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
@@ -91,7 +92,9 @@ def load_library() -> ctypes.CDLL:
     # The HIP runtime maps all streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4) and reads
     # the variable when libamdhip64 is loaded; kernels that share a queue run one after the other.  One context
     # per task thread with 8 threads on 8 MiB map outputs: 12 GB/s with 4 queues, 23 GB/s with 16.  A JVM gets
-    # the same through spark.executorEnv.GPU_MAX_HW_QUEUES; an explicit setting wins.
+    # the same through spark.executorEnv.GPU_MAX_HW_QUEUES; an explicit setting wins.  Whatever the
+    # value, the library spreads its contexts over the runtime's per-priority queue pools (OPT_STREAM_CLASS), so 3 x cap - 3
+    # contexts get a queue of their own: 9 at the default of 4.
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     path = library_path()
     if not os.path.exists(path):

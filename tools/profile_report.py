@@ -41,6 +41,41 @@ SETS = {
 # round 5: the HBM-bound stage lines (bench.py --hbm-stages-only): traffic per launch of each kernel, keyed for run_hbm_stages
 HBM_KERNELS = {"checksum_segments_kernel<1>": "hbm-stages:adler32", "checksum_segments_kernel<2>": "hbm-stages:crc32",
                "xxh32_items_quad_kernel<false>": "hbm-stages:xxh32"}
+
+
+def queue_report(dispatches):
+    """Markdown lines for the codec dispatches of one kernel trace (summary.json "codec_dispatches", tools/summarize_prof.py):
+    a table per hardware queue, and the time-weighted mean number of codec launches executing.  Streams that share a queue run
+    one after the other, so two contexts on one queue show as two streams in one row whose launches never overlap."""
+    if not dispatches:
+        return ["(no codec dispatches in the trace)"]
+    t_first, t_last = min(d["start_ns"] for d in dispatches), max(d["end_ns"] for d in dispatches)
+    lines = ["| queue | codec launches | streams on it | threads on it | busy ms | share of the window |", "|---|---|---|---|---|---|"]
+    by_q = {}
+    for d in dispatches:
+        by_q.setdefault(d["queue"], []).append(d)
+    for q, ds in sorted(by_q.items(), key=lambda kv: str(kv[0])):
+        busy = sum(d["end_ns"] - d["start_ns"] for d in ds)
+        lines.append(f"| {q} | {len(ds)} | {len({d['stream'] for d in ds})} | {len({d['tid'] for d in ds})} | {busy / 1e6:.2f} | "
+                     f"{busy / max(t_last - t_first, 1):.3f} |")
+    # sweep over start / end stamps: time spent with k launches executing
+    edges = sorted([(d["start_ns"], 1) for d in dispatches] + [(d["end_ns"], -1) for d in dispatches])
+    at, level, prev = {}, 0, edges[0][0]
+    for t, step in edges:
+        at[level] = at.get(level, 0) + (t - prev)
+        level, prev = level + step, t
+    window = max(t_last - t_first, 1)
+    busy_any = window - at.get(0, 0)
+    total = sum(d["end_ns"] - d["start_ns"] for d in dispatches)
+    streams, queues = len({d["stream"] for d in dispatches}), len(by_q)
+    lines += ["", f"* streams with codec launches: {streams}, hardware queues they ran on: {queues}"
+                  + (" (every stream has a queue of its own)" if streams == queues else " (streams share a queue)"),
+              f"* mean codec launches executing, over the window from the first launch to the last ({window / 1e6:.1f} ms): {total / window:.3f}",
+              f"* mean codec launches executing, while at least one runs ({busy_any / 1e6:.1f} ms): {total / max(busy_any, 1):.3f}",
+              "* share of the window with k launches executing: " + ", ".join(f"k={k}: {v / window:.3f}" for k, v in sorted(at.items()))]
+    return lines
+
+
 stamp_file = os.path.join(G, "kernel_sources_sha256.txt")
 stamp = open(stamp_file).read().strip() if os.path.exists(stamp_file) else None
 traffic_file = os.path.join(P, "traffic_latest.json")
@@ -53,6 +88,10 @@ for name, (kernel, key, tasks) in SETS.items():
     cmd = open(cmd_file).read().strip().replace(ROOT + "/", "") if os.path.exists(cmd_file) else "bench.py"
     cmd = cmd[cmd.find("bench.py"):] if "bench.py" in cmd else cmd
     d = json.load(open(src))
+    if d.get("codec_dispatches"):  # queue placement of the map side's codec launches (needs only the kernel trace, no counters)
+        report = "\n".join(queue_report(d["codec_dispatches"]))
+        print(f"{name}: codec launches per hardware queue\n{report}")
+        open(os.path.join(G, "prof_" + name, "queues.md"), "w").write(report + "\n")
     k = d["kernels"].get(kernel)
     c = d["pmc"].get(kernel, {})
     if not k or not c:

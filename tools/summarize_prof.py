@@ -14,9 +14,14 @@ def short(name):
     return n.strip()
 
 
-out = {"kernels": {}, "pmc": {}}
+out = {"kernels": {}, "pmc": {}, "codec_dispatches": []}
 for f in sorted(glob.glob(os.path.join(root, "trace", "**", "*.db"), recursive=True)):
     c = sqlite3.connect(f)
+    # every dispatch of the map side's codec kernel with its hardware queue: tools/profile_report.py groups them by queue and
+    # counts how many run at the same time (streams that share a queue never overlap)
+    for name, queue, stream, tid, t0, t1 in c.execute("select name, queue_id, stream_id, tid, start, end from kernels order by start"):
+        if short(name).startswith("lz4_compress"):
+            out["codec_dispatches"].append({"kernel": short(name), "queue": queue, "stream": stream, "tid": tid, "start_ns": t0, "end_ns": t1})
     rows = c.execute("select name, count(*), sum(duration), avg(duration), min(duration), max(duration), "
                      "max(vgpr_count), max(sgpr_count), max(lds_size), max(grid_x), max(workgroup_x) "
                      "from kernels group by name order by sum(duration) desc").fetchall()
