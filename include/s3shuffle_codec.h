@@ -93,7 +93,10 @@ extern "C" {
                                  still 11: + Spark IO encryption (AES/CTR/NoPadding) as a layer on both sides of the codec:
                                  s3s_set_io_encryption, s3s_set_stream_ivs and the read-only key 11.  Additive again: a caller
                                  detects support by the symbols, or by s3s_get_option(ctx, 11) answering 0 instead of
-                                 S3S_E_INVALID */
+                                 S3S_E_INVALID;
+                                 still 11: + S3S_OPT_ZSTD_DECODE_VARIANT (key 13) and the read-only S3S_OPT_ZSTD_DECODE_BLOCKS (key
+                                 14): block-independent Zstandard frames decode one workgroup per block.  Additive: the output
+                                 of every call is unchanged, a library without the keys answers S3S_E_INVALID to them */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
@@ -183,7 +186,7 @@ enum {
   S3S_OPT_IO_ENCRYPTION_KEY_BITS = 11, /* ABI 11, additive, READ-ONLY: 0 (the layer is off), 128, 192 or 256 - the key that
                                     s3s_set_io_encryption holds.  s3s_set_option on it answers S3S_E_INVALID; a library without
                                     the layer answers S3S_E_INVALID to s3s_get_option too, which is how callers detect it */
-  S3S_OPT_STREAM_CLASS = 12      /* ABI 11, additive, READ-ONLY: the hardware-queue pool of the context's stream.  The runtime keeps
+  S3S_OPT_STREAM_CLASS = 12,     /* ABI 11, additive, READ-ONLY: the hardware-queue pool of the context's stream.  The runtime keeps
                                     one pool of GPU_MAX_HW_QUEUES queues (default 4) per stream priority and streams that share a
                                     queue run one after the other, so s3s_create spreads the contexts of a device over the pools
                                     by creation slot (the lowest free one; s3s_destroy returns it): 0 = lowest priority (the first
@@ -191,6 +194,16 @@ enum {
                                     priority beyond that, where contexts share queues.  S3S_STREAM_POOLS=0 in the environment
                                     puts every stream at normal priority (answer 1); =2 fills normal, highest, lowest in that
                                     order.  s3s_set_option on it answers S3S_E_INVALID */
+  S3S_OPT_ZSTD_DECODE_VARIANT = 13, /* ABI 11, additive; tuning, identical output, S3S_CODEC_ZSTD on the reduce side: 1 (default) =
+                                    frames whose header states a content size and a window of at most one block (131072),
+                                    without dictionary id and content checksum - what S3S_OPT_ZSTD_COMPRESS = 1 writes - are
+                                    decoded one workgroup per BLOCK; a frame with one block that needs anything in front of
+                                    itself is decoded again, and judged, by the one-frame-per-wavefront decoder, so bytes,
+                                    return codes and per-entry statuses are those of 0.  0 = one frame per wavefront only.
+                                    Other values: S3S_E_INVALID */
+  S3S_OPT_ZSTD_DECODE_BLOCKS = 14 /* ABI 11, additive, READ-ONLY: the number of blocks of the last S3S_CODEC_ZSTD decode call on
+                                    this context whose frames completed on the block path of key 13, 0 otherwise.
+                                    s3s_set_option on it answers S3S_E_INVALID */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */

@@ -236,6 +236,12 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
       return fail(ctx, S3S_E_INVALID, "option %d is read-only (s3s_set_io_encryption switches the layer)", key);
     case S3S_OPT_STREAM_CLASS:
       return fail(ctx, S3S_E_INVALID, "option %d is read-only (the context's creation slot decides it)", key);
+    case S3S_OPT_ZSTD_DECODE_VARIANT:
+      if (value != 0 && value != 1) return fail(ctx, S3S_E_INVALID, "zstd decode variant must be 0 (one frame per wavefront) or 1 (block path where eligible)");
+      ctx->zstd_decode_variant = (int)value;
+      return S3S_OK;
+    case S3S_OPT_ZSTD_DECODE_BLOCKS:
+      return fail(ctx, S3S_E_INVALID, "option %d is read-only (the last Zstandard decode call sets it)", key);
   }
   return fail(ctx, S3S_E_INVALID, "unknown option %d", key);
 }
@@ -255,6 +261,8 @@ int64_t s3s_get_option(const s3s_ctx* ctx, int key) {
     case S3S_OPT_LZF_COMPRESS: return ctx->lzf_compress;
     case S3S_OPT_IO_ENCRYPTION_KEY_BITS: return ctx->enc_key_bits;
     case S3S_OPT_STREAM_CLASS: return ctx->stream_class;
+    case S3S_OPT_ZSTD_DECODE_VARIANT: return ctx->zstd_decode_variant;
+    case S3S_OPT_ZSTD_DECODE_BLOCKS: return ctx->zstd_decode_blocks;
   }
   return S3S_E_INVALID;
 }

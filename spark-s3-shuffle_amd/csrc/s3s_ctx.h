@@ -33,6 +33,7 @@ enum BufId {
   B_IVS,        // IO encryption, map side: one IV per partition of the call
   B_CRYPT,      // IO encryption, reduce side: the fetched range decrypted, IVs dropped
   B_CRYPT_OFF,  // IO encryption: stored / plain partition offsets of the AES-CTR pass where they are not B_INDEX
+  B_ZBLOCKS, B_ZBLOCK_LIT,  // zstd block path (zstd_decode_blocks.hip): control word + frame and block tables; literal buffers of its grid
   B_PLAN,  // batched map side: the call's small arrays in one arena, one upload and one download (PackedPlan, stream_placement.h)
   B_COUNT
 };
@@ -62,6 +63,8 @@ struct s3s_ctx {
   int snappy_variant = 1;
   int zstd_compress = 0;  // S3S_OPT_ZSTD_COMPRESS: the compress entry points take S3S_CODEC_ZSTD (off: S3S_E_UNSUPPORTED, as before ABI 11)
   int lzf_compress = 0;   // S3S_OPT_LZF_COMPRESS: the same switch for S3S_CODEC_LZF
+  int zstd_decode_variant = 1;  // S3S_OPT_ZSTD_DECODE_VARIANT: 1 = block-independent frames one workgroup per block, 0 = one frame per wavefront only
+  int zstd_decode_blocks = 0;   // S3S_OPT_ZSTD_DECODE_BLOCKS: blocks of the last Zstandard decode call whose frames completed on the block path
   s3s::DevBuf buf[s3s::B_COUNT];
   int cu_count = 256;  // compute units of the device (persistent grids: resident wavefronts per CU x this)
   void* h_stage = nullptr;  // pinned

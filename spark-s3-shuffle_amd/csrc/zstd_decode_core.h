@@ -625,12 +625,15 @@ struct FrameOut {
 struct FrameHdr {
   int64_t bytes;     // header bytes (skippable frame: the whole frame)
   int64_t fcs;       // frame content size, -1 when absent
+  int64_t window;    // Window_Size (RFC 8878 3.1.1.1.2); a single-segment frame's window is its content size
   int has_check, skippable;
+  int has_did;       // a Dictionary_ID field is present (its value is 0, anything else was refused)
 };
 // Frame header at src[0, size) (RFC 8878 3.1.1.1); both sides of a partition walk the same headers.
 ZS_HD int frame_header(const uint8_t* src, int64_t size, FrameHdr* fh) {
   fh->fcs = -1;
-  fh->has_check = fh->skippable = 0;
+  fh->window = 0;
+  fh->has_check = fh->skippable = fh->has_did = 0;
   if (size < 4) return ZS_FAIL();
   const uint32_t magic = rd_le(src, 4);
   if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {  // skippable frame
@@ -648,11 +651,17 @@ ZS_HD int frame_header(const uint8_t* src, int64_t size, FrameHdr* fh) {
   fh->has_check = (int)((fhd >> 2) & 1);
   if (fhd & 0x08) return ZS_FAIL();  // reserved bit
   int64_t ip = 5;
-  if (!single) ip++;  // window descriptor: a block is at most kMaxBlock whatever it says, and history is the whole frame here
+  if (!single) {  // window descriptor: a block is at most kMaxBlock whatever it says, and history is the whole frame here -
+    // the decoder accepts every value; the block-parallel path reads it as a promise (frame_candidate below)
+    const uint32_t wd = src[ip++];
+    const int64_t base = (int64_t)1 << (10 + (wd >> 3));
+    fh->window = base + (base >> 3) * (int64_t)(wd & 7);
+  }
   static const int did_bytes[4] = {0, 1, 2, 4};
   if (ip + did_bytes[did_flag] > size) return ZS_FAIL();
   if (did_flag && rd_le(src + ip, did_bytes[did_flag]) != 0) return ZS_UNSUPPORTED;  // dictionaries are not used by Spark
   ip += did_bytes[did_flag];
+  fh->has_did = did_flag != 0;
   const int fcs_bytes = fcs_flag == 0 ? (single ? 1 : 0) : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8));
   if (ip + fcs_bytes > size) return ZS_FAIL();
   if (fcs_bytes) {
@@ -662,6 +671,7 @@ ZS_HD int frame_header(const uint8_t* src, int64_t size, FrameHdr* fh) {
     fh->fcs = (int64_t)v;
     ip += fcs_bytes;
   }
+  if (single) fh->window = fh->fcs;
   fh->bytes = ip;
   return ZS_OK;
 }
@@ -791,6 +801,9 @@ ZS_HD int pipe_wait_ready(LitPipe& lp, int32_t want) {
 typedef __attribute__((address_space(3))) Work* WorkLds;
 typedef __attribute__((address_space(1))) const uint8_t* GlobalIn;
 typedef __attribute__((address_space(1))) uint8_t* GlobalOut;
+// kBlock (zstd_decode_blocks.hip): the block stands alone - a repeat code means history from before it, so the loop stops in
+// front of one like in front of anything else that is not plain (a source in front of the block does already: hist is 0 there).
+template <bool kBlock>
 __device__ __attribute__((noinline)) void seq_fast(WorkLds w, int lane) {
   const GlobalIn bits = (GlobalIn)w->fast.bits;
   const GlobalOut bdst = (GlobalOut)w->fast.bdst;
@@ -842,6 +855,7 @@ __device__ __attribute__((noinline)) void seq_fast(WorkLds w, int lane) {
     // (the repeat-offset history too is vector arithmetic on values every lane holds: the two units share the work, and this
     //  kernel is bound by what they can issue.  rep0..2 live in vector registers; the offset comes back to the scalar side.)
     const bool is_rep = oval <= 3;
+    if (kBlock && ZS_UNI32(is_rep ? 1u : 0u)) break;
     const uint32_t idx = oval - 1 + (llen == 0 ? 1u : 0u);
     uint32_t rv = rep0;
     rv = idx == 1 ? rep1 : rv;
@@ -923,10 +937,22 @@ __device__ __attribute__((noinline)) void seq_fast(WorkLds w, int lane) {
 // decodes a block's Huffman literals right here into lit_buf (kMaxBlock + 32 bytes, lit_stride 0); on the device they come
 // from the literal wavefront through lit_buf + (hblock & 1) * lit_stride.  hblock: Huffman-coded blocks of the partition so
 // far (runs on over the partition's frames; both sides count alike).
+//
+// kBlock = true is the body of ONE block on its own (decode_block below, the block-parallel path): src points at the block's
+// 3-byte header, dst at the block's first output byte, cap is the length the block must decode to EXACTLY, and the state is
+// that of a frame's first block - repeat history 1 / 4 / 8, no previous table or tree.  What a block needs from in front of
+// itself makes it fail here (ZS_BAD): treeless literals, a Repeat-mode table, an Offset_Value <= 3, a match source before
+// dst.  hblock is then the index of the literal buffer hand-over (the caller counts, see zstd_decode_blocks.hip).
+template <bool kBlock = false>
 ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, uint8_t* dst, int64_t cap, bool execute,
                        uint8_t* lit_buf, int64_t lit_stride, int32_t& hblock, Lanes L, FrameOut* out) {
   FrameHdr fh;
-  {
+  if (kBlock) {
+    fh.bytes = 0;
+    fh.fcs = cap;
+    fh.window = 0;
+    fh.has_check = fh.skippable = fh.has_did = 0;
+  } else {
     const int rc = frame_header(src, size, &fh);
     if (rc != ZS_OK) return rc;
   }
@@ -983,6 +1009,7 @@ ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, u
         const int rc = literals_header(b, bsize, &lh);
         if (rc != ZS_OK) return rc;
       }
+      if (kBlock && lh.ltype == 3) return ZS_FAIL();  // treeless: the tree is a previous block's
       const int64_t regen = lh.regen;
       const uint8_t* lit = nullptr;   // where the regenerated literals are (raw: inside src)
       int lit_rle = -1;
@@ -1128,7 +1155,7 @@ ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, u
               f.hist_lo = (uint32_t)(uint64_t)bop;
               f.hist_hi = (uint32_t)((uint64_t)bop >> 32);
               __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-              seq_fast((WorkLds)&w, L.lane);
+              seq_fast<kBlock>((WorkLds)&w, L.lane);
               const uint32_t ni = ZS_UNI32(f.i);
               if (ni == (uint32_t)i) {
                 fast_pause = 3;
@@ -1211,6 +1238,7 @@ ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, u
           // whatever the container held.  Valid streams never get here, and damaged ones were stopped by the partition's
           // Adler32 / CRC32 before the decoder saw them.
           uint32_t bad = r.pos < 0 ? 1u : 0u;
+          if (kBlock) bad |= oval <= 3 ? 1u : 0u;  // a repeat code reaches for offsets of the blocks before
           // offset with the repeat history.  Three scalars on purpose: an array indexed by the repeat code lives in scratch
           // memory on the device - a store and a load round trip on every sequence's critical path.  Selects instead of
           // branches, and ONE exit for everything that can be wrong with a sequence: a branch costs this loop an exec-mask
@@ -1284,7 +1312,7 @@ ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, u
       if (bout > (uint32_t)kMaxBlock) return ZS_FAIL();
       op = bop + bout;
       ip += bsize;
-      if (huf_block) {
+      if (!kBlock && huf_block) {
         hblock++;
 #ifdef S3S_ZSTD_DEVICE
         if (execute) pipe_set(&lp.consumed, hblock, L);  // (a release: this block's reads of its literal buffer are done)
@@ -1292,7 +1320,7 @@ ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, u
       }
       if (execute) ZS_FENCE();
     }
-    if (last) break;
+    if (kBlock || last) break;
   }
   if (has_check) {
     if (ip + 4 > size) return ZS_FAIL();
@@ -1309,12 +1337,159 @@ ZS_HD int decode_frame(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, u
   return ZS_OK;
 }
 
-// All frames of one partition (concatenated streams of a multi-spill map task).  *total = decoded bytes.
+// ---- block-independent frames ---------------------------------------------------------------------------------------
+// A frame whose header promises a window of at most one block (Window_Size <= kMaxBlock) and states its content size can have
+// every block decoded on its own: block k lands at k * kMaxBlock of the frame's output and needs nothing in front of it - IF
+// the writer kept the promise.  The header walk below only finds the candidates and their blocks; whether a block really stands
+// alone is decided while it is decoded (decode_block), and a frame with one block that does not is decoded again by
+// decode_frame, whose verdict is the frame's.
+struct BlockJob {      // one block of a candidate frame
+  int64_t src_off;     // its 3-byte header, from the partition's first byte
+  int64_t out_off;     // its first output byte, from the partition's first output byte
+  int32_t bsize, type; // Block_Size, Block_Type (0 raw, 1 RLE, 2 compressed)
+  int32_t expect;      // the bytes it must decode to: kMaxBlock, the frame's last block what is left of the content size
+  int32_t frame;       // its FrameEnt
+};
+struct FrameEnt {      // one candidate frame
+  int64_t src_off, consumed;  // where it starts in the partition, the bytes it occupies
+  int64_t out_off, fcs;       // where its content starts in the partition's output, Frame_Content_Size
+  int32_t n_blocks, part;
+  int32_t done;        // blocks the block path has decoded to their expected length
+  int32_t dependent;   // a block needed history, failed or was never tried: the frame belongs to decode_frame
+};
+ZS_HD bool frame_complete(const FrameEnt& f) { return f.dependent == 0 && f.done == f.n_blocks; }
+
+// From the frame header alone: may the blocks of this frame be tried one by one?  window_rule = false is for tests (frames
+// of writers that do use history then become candidates, and must all be found dependent).  min_blocks (>= 2): the caller's
+// floor - a call of thousands of short frames fills the machine one frame per wavefront already (zstd_decode_blocks.hip).
+ZS_HD bool frame_candidate(const FrameHdr& fh, bool window_rule = true, int32_t min_blocks = 2) {
+  if (fh.skippable || fh.fcs < 0 || fh.has_did || fh.has_check) return false;
+  if (window_rule && fh.window > kMaxBlock) return false;
+  return fh.fcs > (int64_t)(min_blocks - 1) * kMaxBlock;  // at least two blocks
+}
+ZS_HD int32_t frame_block_count(int64_t fcs) { return (int32_t)((fcs + kMaxBlock - 1) / kMaxBlock); }
+
+// The block headers of the candidate frame at src[0, size) (size: to the end of the partition): n = frame_block_count(fcs)
+// entries of jobs.  True when the headers are those of n blocks of which every one but the last can only decode to kMaxBlock
+// bytes (Raw / RLE: says so itself), the last one is marked last, they all lie inside the partition and what follows is the
+// partition's end or another frame.  False leaves every entry inert (expect 0).
+ZS_HD bool scan_frame_blocks(const uint8_t* src, int64_t size, const FrameHdr& fh, int64_t frame_src_off, int64_t frame_out_off,
+                             int32_t frame_id, BlockJob* jobs, int64_t* consumed) {
+  const int32_t n = frame_block_count(fh.fcs);
+  int64_t ip = fh.bytes;
+  bool ok = true;
+  for (int32_t k = 0; k < n && ok; k++) {
+    if (ip + 3 > size) { ok = false; break; }
+    const uint32_t bh = rd_le(src + ip, 3);
+    const int last = (int)(bh & 1), type = (int)((bh >> 1) & 3);
+    const int64_t bsize = bh >> 3;
+    const int64_t stored = type == 1 ? 1 : bsize;
+    if (type == 3 || bsize > kMaxBlock || (type == 2 && bsize < 2) || last != (k == n - 1 ? 1 : 0) || ip + 3 + stored > size ||
+        (type < 2 && k < n - 1 && bsize != kMaxBlock)) {
+      ok = false;
+      break;
+    }
+    BlockJob j;
+    j.src_off = frame_src_off + ip;
+    j.out_off = frame_out_off + (int64_t)k * kMaxBlock;
+    j.bsize = (int32_t)bsize;
+    j.type = type;
+    j.expect = k < n - 1 ? kMaxBlock : (int32_t)(fh.fcs - (int64_t)kMaxBlock * (n - 1));
+    j.frame = frame_id;
+    jobs[k] = j;
+    ip += 3 + stored;
+  }
+  if (ok) {
+    const int64_t rest = size - ip;
+    if (rest != 0) {
+      if (rest < 4) ok = false;
+      else {
+        const uint32_t magic = rd_le(src + ip, 4);
+        ok = magic == 0xFD2FB528u || (magic & 0xFFFFFFF0u) == 0x184D2A50u;
+      }
+    }
+  }
+  if (!ok) {
+    BlockJob j;
+    j.src_off = j.out_off = 0;
+    j.bsize = j.type = j.expect = 0;
+    j.frame = frame_id;
+    for (int32_t k = 0; k < n; k++) jobs[k] = j;
+    return false;
+  }
+  *consumed = ip;
+  return true;
+}
+
+// The candidate frames at the head of one partition: frames[0, return value), their blocks in the table `reserve` hands out
+// (reserve(n): first index of n entries of jobs, or -1).  The walk ends at the first frame that is no candidate (what lies
+// behind a frame without a content size has no known output position), that would not fit cap, or whose headers do not add
+// up - that one is still entered, as dependent, with inert blocks.
+template <class Reserve>
+ZS_HD int32_t scan_partition(const uint8_t* src, int64_t size, int64_t cap, int32_t part, bool window_rule, FrameEnt* frames,
+                             int32_t frame_cap, int32_t frame_id0, BlockJob* jobs, Reserve reserve, int32_t min_blocks = 2) {
+  int64_t ip = 0, op = 0;
+  int32_t nf = 0;
+  while (ip < size && nf < frame_cap) {
+    FrameHdr fh;
+    if (frame_header(src + ip, size - ip, &fh) != ZS_OK) break;
+    if (!frame_candidate(fh, window_rule, min_blocks) || fh.fcs > cap - op) break;
+    const int32_t n = frame_block_count(fh.fcs);
+    const int64_t base = reserve(n);
+    if (base < 0) break;
+    int64_t consumed = 0;
+    const bool ok = scan_frame_blocks(src + ip, size - ip, fh, ip, op, frame_id0 + nf, jobs + base, &consumed);
+    FrameEnt f;
+    f.src_off = ip;
+    f.consumed = consumed;
+    f.out_off = op;
+    f.fcs = fh.fcs;
+    f.n_blocks = n;
+    f.part = part;
+    f.done = 0;
+    f.dependent = ok ? 0 : 1;
+    frames[nf++] = f;
+    if (!ok) break;
+    ip += consumed;
+    op += fh.fcs;
+  }
+  return nf;
+}
+
+// One block of a candidate frame on its own: blk[0, 3 + stored bytes) into dst[0, expect).  ZS_OK = the block stands alone and
+// decoded to exactly `expect` bytes; anything else (a format error, ZS_CAPACITY, history from before the block) means "not on
+// this path", never a verdict.  Nothing outside dst[0, expect) is written either way.
+ZS_HD int decode_block(Work& w, LitPipe& lp, const uint8_t* blk, int64_t avail, uint8_t* dst, int32_t expect, uint8_t* lit_buf,
+                       int64_t lit_stride, int32_t handover, Lanes L) {
+  FrameOut fo;
+  int32_t hb = handover;
+  return decode_frame<true>(w, lp, blk, avail, dst, expect, true, lit_buf, lit_stride, hb, L, &fo);
+}
+
+// the frames of a partition the block path has completed: decode_partition and the literal side step over them
+struct SkipCursor {
+  const FrameEnt* f;
+  int32_t n, at;
+};
+
+// All frames of one partition (concatenated streams of a multi-spill map task).  *total = decoded bytes.  kSkip: frames that
+// the block path completed (sc) are stepped over, *blocks_done counts their blocks.
+template <bool kSkip = false>
 ZS_HD int decode_partition(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, uint8_t* dst, int64_t cap, bool execute,
-                           uint8_t* lit_buf, int64_t lit_stride, Lanes L, int64_t* total, int64_t* lit_need = nullptr) {
+                           uint8_t* lit_buf, int64_t lit_stride, Lanes L, int64_t* total, int64_t* lit_need = nullptr,
+                           SkipCursor sc = SkipCursor{nullptr, 0, 0}, int32_t* blocks_done = nullptr) {
   int64_t ip = 0, op = 0, need = 0;
   int32_t hblock = 0;
   while (ip < size) {
+    if (kSkip && sc.at < sc.n && sc.f[sc.at].src_off == ip) {
+      const FrameEnt f = sc.f[sc.at++];
+      if (frame_complete(f)) {
+        ip += f.consumed;
+        op += f.fcs;
+        *blocks_done += f.n_blocks;
+        continue;
+      }
+    }
     FrameOut fo;
     const int rc = decode_frame(w, lp, src + ip, size - ip, execute ? dst + op : dst, execute ? cap - op : 0, execute, lit_buf,
                                 lit_stride, hblock, L, &fo);
@@ -1348,10 +1523,19 @@ struct LitWalker {
   int64_t bsize;
 };
 // to the next Huffman-coded literals section (have = 1) or the end of the partition (done = 1)
-ZS_HD void walker_advance(LitWalker& k, LitPipe& lp, Lanes L) {
+template <bool kSkip = false>
+ZS_HD void walker_advance(LitWalker& k, LitPipe& lp, Lanes L, SkipCursor* sc = nullptr) {
   for (;;) {
     if (!k.in_frame) {
       if (k.ip >= k.size) { k.done = 1; return; }
+      if (kSkip && sc->at < sc->n && sc->f[sc->at].src_off == k.ip) {  // (the same decision as decode_partition's, from the same memory)
+        const FrameEnt f = sc->f[sc->at];
+        sc->at++;
+        if (frame_complete(f)) {
+          k.ip += f.consumed;
+          continue;
+        }
+      }
       FrameHdr fh;
       if (frame_header(k.src + k.ip, k.size - k.ip, &fh) != ZS_OK) break;
       k.ip += fh.bytes;
@@ -1390,7 +1574,8 @@ ZS_HD void walker_advance(LitWalker& k, LitPipe& lp, Lanes L) {
   k.done = 1;
 }
 // n_parts (1 or 2) partitions of the workgroup: whichever has a block to regenerate and a free buffer goes next
-ZS_HD void literal_side(LitPipe* lps, LitWalker* ks, int n_parts, Lanes L) {
+template <bool kSkip = false>
+ZS_HD void literal_side(LitPipe* lps, LitWalker* ks, int n_parts, Lanes L, SkipCursor* scs = nullptr) {
   int32_t idle = 0;
   for (;;) {
     bool any = false, progressed = false;
@@ -1399,7 +1584,7 @@ ZS_HD void literal_side(LitPipe* lps, LitWalker* ks, int n_parts, Lanes L) {
       LitPipe& lp = lps[t];
       if (k.done) continue;
       if (!k.have) {
-        walker_advance(k, lp, L);
+        walker_advance<kSkip>(k, lp, L, kSkip ? scs + t : nullptr);
         if (k.done) continue;
       }
       any = true;

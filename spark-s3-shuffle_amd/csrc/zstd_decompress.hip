@@ -9,84 +9,17 @@
 //           by pass 1 (the largest regenerated literals section of its blocks).
 // Compression with this codec stays on the JVM: s3s_compress_* answer S3S_E_UNSUPPORTED.
 #define S3S_ZSTD_DEVICE 1
-#include "s3s_ctx.h"
-#include "zstd_decode_core.h"
+#include "zstd_decode_blocks.h"
 
 #include <vector>
 
 namespace s3s {
 namespace {
 
-struct ZPart {       // one partition of one range
-  const uint8_t* src;
-  int64_t size;
-  uint8_t* dst;      // pass 2: where its decoded bytes go
-  int64_t cap;       // pass 2: bytes available there
-  int64_t lit_off;   // pass 2: offset of its literals scratch: two buffers lit_stride apart (block k uses buffer k & 1)
-  int64_t lit_stride;
-};
-struct ZRes {
-  int64_t total;     // decoded bytes
-  int64_t lit_need;  // scratch the partition needs in pass 2
-  int32_t rc;        // ZS_OK / ZS_BAD / ZS_CAPACITY / ZS_UNSUPPORTED (= the S3S_E_* values)
-  int32_t pad;
-};
-
-// Three wavefronts per workgroup, two partitions (round 4).  Wavefronts 0 and 1 are the SEQUENCE sides of partitions 2b and
-// 2b + 1: headers, FSE tables, the sequence loop and its copies.  Wavefront 2 is the LITERAL side of both: it walks the same
-// headers and regenerates the Huffman-coded literals of a partition's NEXT block while its sequence wavefront executes this
-// one (a level-1 TeraSort frame spent 8.5 of its 38 ms in Huffman streams on 4 of 64 lanes, and the rest never needed those
-// lanes' results before the next block; one literal wavefront keeps up with two sequence sides).  They meet through four
-// counters in LDS per partition (s3s_zstd::LitPipe) and two literal buffers per partition.  Registers: the sequence side
-// needs 186 VGPRs when left alone; three wavefronts per SIMD (12 per CU = 4 workgroups = 8 partitions in flight, what the
-// one-wavefront-per-partition kernel had) leave it 168.
-constexpr int kZstdThreads = 3 * kWave;
+// (ZPart / ZRes and the kernel's body: zstd_decode_blocks.h - the block path's kernel behind it shares them)
 __global__ __launch_bounds__(kZstdThreads, 3) void zstd_partitions_kernel(const ZPart* __restrict__ parts, int32_t n, int execute,
                                                                          uint8_t* __restrict__ lit_base, ZRes* __restrict__ res) {
-  __shared__ s3s_zstd::Work w[2];
-  __shared__ s3s_zstd::LitPipe lp[2];
-  __shared__ s3s_zstd::LitWalker ks[2];  // (the literal wavefront's own state: indexed by partition, so not in registers)
-  const int p0 = 2 * (int)blockIdx.x;
-  if (p0 >= n) return;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  s3s_zstd::Lanes L{(int)(threadIdx.x & (kWave - 1)), kWave};
-  if (threadIdx.x < 2) lp[threadIdx.x].ready = lp[threadIdx.x].consumed = lp[threadIdx.x].err = lp[threadIdx.x].quit = 0;
-  __syncthreads();
-  if (wave == 2) {
-    if (execute == 0) return;
-    const int np = n - p0 < 2 ? n - p0 : 2;
-    for (int t = 0; t < np; t++) {
-      const ZPart zp = parts[p0 + t];
-      ks[t].src = zp.src;
-      ks[t].size = zp.size;
-      ks[t].ip = 0;
-      ks[t].lit_buf = lit_base ? lit_base + zp.lit_off : nullptr;
-      ks[t].lit_stride = zp.lit_stride;
-      ks[t].hblock = 0;
-      ks[t].in_frame = ks[t].has_check = ks[t].have = 0;
-      ks[t].done = zp.size > 0 ? 0 : 1;
-    }
-    s3s_zstd::literal_side(lp, ks, np, L);
-    return;
-  }
-  const int p = p0 + wave;
-  if (p >= n) return;
-  __builtin_amdgcn_s_setprio(3);  // (the sequence side is the partition's critical path, the literal wavefront has slack: + 4.7 %)
-  const ZPart zp = parts[p];
-  int64_t total = 0, need = 0;
-  int rc = s3s_zstd::ZS_OK;
-  if (zp.size > 0)
-    rc = s3s_zstd::decode_partition(w[wave], lp[wave], zp.src, zp.size, zp.dst, zp.cap, execute != 0,
-                                    lit_base ? lit_base + zp.lit_off : nullptr, zp.lit_stride, L, &total, &need);
-  s3s_zstd::pipe_set(&lp[wave].quit, 1, L);  // (a literal side still waiting for a buffer leaves)
-  if (L.lane == 0) {
-    ZRes r;
-    r.total = total;
-    r.lit_need = need;
-    r.rc = rc;
-    r.pad = 0;
-    res[p] = r;
-  }
+  zstd_partitions_body<false>(parts, n, execute, lit_base, res, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ---- single pass (round 4): partitions decoded at guessed capacities are moved back to back ------------------------------
@@ -129,6 +62,7 @@ static_assert(s3s_zstd::ZS_BAD == S3S_E_BAD_FRAME && s3s_zstd::ZS_CAPACITY == S3
 // Per range: status / out_len / bad_partition as s3s_decompress_range_device reports them.  Returns the first error.
 int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, int32_t n_ranges, bool size_only, bool* regular_end) {
   if (regular_end) *regular_end = false;  // true: every range has its own verdict (the return value is the first bad one's)
+  ctx->zstd_decode_blocks = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (auto& v : ctx->stage_ms) v = 0;
   int64_t n_parts64 = 0, n_segs64 = 0;
@@ -161,7 +95,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
   auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
   const size_t o_parts = 0, o_res = al(o_parts + sizeof(ZPart) * (size_t)n_parts), o_off = al(o_res + sizeof(ZRes) * (size_t)n_parts),
                o_seg = al(o_off + 8 * ((size_t)n_parts + (size_t)n_ranges)), o_sums = al(o_seg + 4 * ((size_t)n_parts + (size_t)n_ranges)),
-               stage_total = o_sums + 8 * (size_t)n_parts + 64;
+               o_ctrl = al(o_sums + 8 * (size_t)n_parts), stage_total = o_ctrl + sizeof(ZBlockCtrl) + 64;
   int rc;
   if ((rc = ensure_stage(ctx, stage_total))) return rc;
   uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
@@ -170,6 +104,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
   int64_t* h_off = reinterpret_cast<int64_t*>(hs + o_off);
   int32_t* h_seg = reinterpret_cast<int32_t*>(hs + o_seg);
   int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);
+  ZBlockCtrl* h_ctrl = reinterpret_cast<ZBlockCtrl*>(hs + o_ctrl);
   record(ctx, 0);
   // ---- per-partition Adler32 / CRC32 over the compressed bytes (S3ChecksumValidationStream) ---------------------
   if (checksum_algo != S3S_CHECKSUM_NONE) {
@@ -274,10 +209,21 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
     uint8_t* scr = dev<uint8_t>(ctx, B_ZSCRATCH);
     for (int32_t q = 0; q < n_parts; q++) h_parts[q].dst = scr + (uintptr_t)h_parts[q].dst;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_RANGES].p, h_parts, sizeof(ZPart) * (size_t)n_parts, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(zstd_partitions_kernel, dim3((unsigned)((n_parts + 1) / 2)), dim3(kZstdThreads), 0, ctx->stream, dev<ZPart>(ctx, B_RANGES),
-                       n_parts, 1, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES));
+    // Block-independent frames: a scan of the headers and one workgroup per block, in front of the kernel that
+    // gives a frame to a wavefront.  Everything is decided on the device, so the call waits where it always did: the
+    // per-partition kernel steps over the frames the block path completed and decodes every other one as ever, into the same
+    // place.  plan.on = false (variant 0, or no partition large enough to hold such a frame): today's launches, nothing else.
+    ZBlockPlan plan;
+    if (ctx->zstd_decode_variant == 1 && (rc = zstd_blocks_launch(ctx, h_parts, dev<ZPart>(ctx, B_RANGES), n_parts, &plan))) return rc;
+    if (plan.on) {
+      zstd_partitions_skip_launch(ctx, dev<ZPart>(ctx, B_RANGES), n_parts, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES), plan);
+    } else {
+      hipLaunchKernelGGL(zstd_partitions_kernel, dim3((unsigned)((n_parts + 1) / 2)), dim3(kZstdThreads), 0, ctx->stream, dev<ZPart>(ctx, B_RANGES),
+                         n_parts, 1, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES));
+    }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(h_res, ctx->buf[B_FRAMES].p, sizeof(ZRes) * (size_t)n_parts, hipMemcpyDeviceToHost, ctx->stream));
+    if (plan.on) HIP_TRY(ctx, hipMemcpyAsync(h_ctrl, plan.d_ctrl, sizeof(ZBlockCtrl), hipMemcpyDeviceToHost, ctx->stream));
     record(ctx, 2);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // verdicts; a partition that outgrew its guess sends the whole call to the two-pass form
@@ -315,6 +261,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
       }
     }
     if (!outgrown) {
+      if (plan.on) ctx->zstd_decode_blocks = h_ctrl->blocks_done;
       std::vector<ZPiece> pcs;  // (source of an asynchronous copy: lives until the stream has been synchronised below)
       if (n_pieces > 0) {
         if ((rc = ensure(ctx, B_ZPIECES, sizeof(ZPiece) * (size_t)n_pieces))) return rc;
@@ -428,12 +375,21 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
   // ---- pass 2: decode ------------------------------------------------------------------------------------------------------
   if ((rc = ensure(ctx, B_SLOTS, (size_t)lit_total + 64))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_RANGES].p, h_parts, sizeof(ZPart) * (size_t)n_parts, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(zstd_partitions_kernel, dim3((unsigned)((n_parts + 1) / 2)), dim3(kZstdThreads), 0, ctx->stream, dev<ZPart>(ctx, B_RANGES),
-                     n_parts, 1, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES));
+  // (the block path as in the single pass: the sizes and verdicts above are the size pass's, here only bytes are produced)
+  ZBlockPlan plan;
+  if (ctx->zstd_decode_variant == 1 && (rc = zstd_blocks_launch(ctx, h_parts, dev<ZPart>(ctx, B_RANGES), n_parts, &plan))) return rc;
+  if (plan.on) {
+    zstd_partitions_skip_launch(ctx, dev<ZPart>(ctx, B_RANGES), n_parts, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES), plan);
+  } else {
+    hipLaunchKernelGGL(zstd_partitions_kernel, dim3((unsigned)((n_parts + 1) / 2)), dim3(kZstdThreads), 0, ctx->stream, dev<ZPart>(ctx, B_RANGES),
+                       n_parts, 1, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES));
+  }
   HIP_TRY(ctx, hipGetLastError());
   record(ctx, 3);
   HIP_TRY(ctx, hipMemcpyAsync(h_res, ctx->buf[B_FRAMES].p, sizeof(ZRes) * (size_t)n_parts, hipMemcpyDeviceToHost, ctx->stream));
+  if (plan.on) HIP_TRY(ctx, hipMemcpyAsync(h_ctrl, plan.d_ctrl, sizeof(ZBlockCtrl), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (plan.on) ctx->zstd_decode_blocks = h_ctrl->blocks_done;
   if (ctx->profile) {
     float ms = 0;
     hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]); ctx->stage_ms[S3S_STAGE_TOTAL] = ms;

@@ -24,6 +24,8 @@ OPT_ZSTD_COMPRESS = 9  # ABI 11: 1 = write decode-compatible Zstandard frames on
 OPT_LZF_COMPRESS = 10  # ABI 11, additive key: 1 = write decode-compatible LZF streams on the map side (not compress-lzf's bytes); default 0
 OPT_STREAM_CLASS = 12  # ABI 11, additive, read-only: queue pool of the context's stream (0 lowest priority, 1 normal, 2 highest, 3 shared)
 OPT_IO_ENCRYPTION_KEY_BITS = 11  # ABI 11, additive, read-only: 0 / 128 / 192 / 256 - the key Codec.set_io_encryption holds
+OPT_ZSTD_DECODE_VARIANT = 13  # ABI 11, additive: 1 (default) = block-independent Zstandard frames one workgroup per block, 0 = one frame per wavefront
+OPT_ZSTD_DECODE_BLOCKS = 14  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the block path
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
 STATUS_NOT_RUN = -100  # per-entry status of a batch call that failed as a call before this entry had a verdict (ABI 6)
@@ -248,6 +250,11 @@ class Codec:
     @property
     def io_encryption_key_bits(self) -> int:
         return self.get_option(OPT_IO_ENCRYPTION_KEY_BITS)
+
+    @property
+    def zstd_decode_blocks(self) -> int:
+        """Blocks of the last Zstandard decode call whose frames completed on the block path (OPT_ZSTD_DECODE_VARIANT = 1), else 0."""
+        return self.get_option(OPT_ZSTD_DECODE_BLOCKS)
 
     def stage_ms(self, stage: int) -> float:
         return float(self._lib.s3s_stage_ms(self._h, stage))
