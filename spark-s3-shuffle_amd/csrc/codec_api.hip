@@ -242,6 +242,12 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
       return S3S_OK;
     case S3S_OPT_ZSTD_DECODE_BLOCKS:
       return fail(ctx, S3S_E_INVALID, "option %d is read-only (the last Zstandard decode call sets it)", key);
+    case S3S_OPT_ZSTD_DECODE_STAGED:
+      if (value != 0 && value != 1) return fail(ctx, S3S_E_INVALID, "zstd staged decode must be 0 (off) or 1 (staged path where eligible)");
+      ctx->zstd_decode_staged = (int)value;
+      return S3S_OK;
+    case S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS:
+      return fail(ctx, S3S_E_INVALID, "option %d is read-only (the last Zstandard decode call sets it)", key);
   }
   return fail(ctx, S3S_E_INVALID, "unknown option %d", key);
 }
@@ -263,6 +269,8 @@ int64_t s3s_get_option(const s3s_ctx* ctx, int key) {
     case S3S_OPT_STREAM_CLASS: return ctx->stream_class;
     case S3S_OPT_ZSTD_DECODE_VARIANT: return ctx->zstd_decode_variant;
     case S3S_OPT_ZSTD_DECODE_BLOCKS: return ctx->zstd_decode_blocks;
+    case S3S_OPT_ZSTD_DECODE_STAGED: return ctx->zstd_decode_staged;
+    case S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS: return ctx->zstd_decode_staged_blocks;
   }
   return S3S_E_INVALID;
 }

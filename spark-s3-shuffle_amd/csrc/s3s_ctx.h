@@ -34,6 +34,7 @@ enum BufId {
   B_CRYPT,      // IO encryption, reduce side: the fetched range decrypted, IVs dropped
   B_CRYPT_OFF,  // IO encryption: stored / plain partition offsets of the AES-CTR pass where they are not B_INDEX
   B_ZBLOCKS, B_ZBLOCK_LIT,  // zstd block path (zstd_decode_blocks.hip): control word + frame and block tables; literal buffers of its grid
+  B_ZSTAGED, B_ZSTAGED_POOL,  // zstd staged path (zstd_decode_staged.hip): control word + frame and block tables; literal and sequence-record staging
   B_PLAN,  // batched map side: the call's small arrays in one arena, one upload and one download (PackedPlan, stream_placement.h)
   B_COUNT
 };
@@ -65,6 +66,8 @@ struct s3s_ctx {
   int lzf_compress = 0;   // S3S_OPT_LZF_COMPRESS: the same switch for S3S_CODEC_LZF
   int zstd_decode_variant = 1;  // S3S_OPT_ZSTD_DECODE_VARIANT: 1 = block-independent frames one workgroup per block, 0 = one frame per wavefront only
   int zstd_decode_blocks = 0;   // S3S_OPT_ZSTD_DECODE_BLOCKS: blocks of the last Zstandard decode call whose frames completed on the block path
+  int zstd_decode_staged = 0;         // S3S_OPT_ZSTD_DECODE_STAGED: 1 = frames with history decode in stages (entropy per block, copies per frame)
+  int zstd_decode_staged_blocks = 0;  // S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS: blocks of the last Zstandard decode call whose frames completed on the staged path
   s3s::DevBuf buf[s3s::B_COUNT];
   int cu_count = 256;  // compute units of the device (persistent grids: resident wavefronts per CU x this)
   void* h_stage = nullptr;  // pinned

@@ -57,11 +57,16 @@ void zstd_partitions_skip_launch(s3s_ctx* ctx, const ZPart* d_parts, int32_t n_p
 // needs 186 VGPRs when left alone; three wavefronts per SIMD (12 per CU = 4 workgroups = 8 partitions in flight, what the
 // one-wavefront-per-partition kernel had) leave it 168.
 // kSkip (zstd_partitions_skip_kernel): both sides step over the frames the block path completed.
-template <bool kSkip>
+// kStaged (zstd_decode_staged.hip, with kSkip): and over the frames the staged path completed, a second list per partition
+// (sp2 / nframes2 / frames2, counted into *staged_done); the block path's list may then be absent (nframes == nullptr).
+template <bool kSkip, bool kStaged = false>
 __device__ __forceinline__ void zstd_partitions_body(const ZPart* __restrict__ parts, int32_t n, int execute, uint8_t* __restrict__ lit_base,
                                                      ZRes* __restrict__ res, const ZScanPart* __restrict__ sp, const int32_t* __restrict__ nframes,
                                                      const s3s_zstd::FrameEnt* __restrict__ frames, ZBlockCtrl* __restrict__ ctrl,
-                                                     s3s_zstd::SkipCursor* scs) {
+                                                     s3s_zstd::SkipCursor* scs, const ZScanPart* __restrict__ sp2 = nullptr,
+                                                     const int32_t* __restrict__ nframes2 = nullptr,
+                                                     const s3s_zstd::FrameEnt* __restrict__ frames2 = nullptr, int32_t* staged_done = nullptr,
+                                                     s3s_zstd::SkipCursor* scs2 = nullptr) {
   __shared__ s3s_zstd::Work w[2];
   __shared__ s3s_zstd::LitPipe lp[2];
   __shared__ s3s_zstd::LitWalker ks[2];  // (the literal wavefront's own state: indexed by partition, so not in registers)
@@ -85,12 +90,18 @@ __device__ __forceinline__ void zstd_partitions_body(const ZPart* __restrict__ p
       ks[t].in_frame = ks[t].has_check = ks[t].have = 0;
       ks[t].done = zp.size > 0 ? 0 : 1;
       if (kSkip) {
-        scs[t].f = frames + sp[p0 + t].frame_base;
-        scs[t].n = nframes[p0 + t];
+        const bool have = !kStaged || nframes != nullptr;
+        scs[t].f = have ? frames + sp[p0 + t].frame_base : nullptr;
+        scs[t].n = have ? nframes[p0 + t] : 0;
         scs[t].at = 0;
       }
+      if (kStaged) {
+        scs2[t].f = frames2 + sp2[p0 + t].frame_base;
+        scs2[t].n = nframes2[p0 + t];
+        scs2[t].at = 0;
+      }
     }
-    s3s_zstd::literal_side<kSkip>(lp, ks, np, L, scs);
+    s3s_zstd::literal_side<kSkip, kStaged>(lp, ks, np, L, scs, scs2);
     return;
   }
   const int p = p0 + wave;
@@ -98,10 +109,16 @@ __device__ __forceinline__ void zstd_partitions_body(const ZPart* __restrict__ p
   __builtin_amdgcn_s_setprio(3);  // (the sequence side is the partition's critical path, the literal wavefront has slack: + 4.7 %)
   const ZPart zp = parts[p];
   int64_t total = 0, need = 0;
-  int32_t blocks = 0;
+  int32_t blocks = 0, blocks2 = 0;
   int rc = s3s_zstd::ZS_OK;
   if (zp.size > 0) {
-    if (kSkip)
+    if (kStaged) {
+      const bool have = nframes != nullptr;
+      rc = s3s_zstd::decode_partition<true, true>(w[wave], lp[wave], zp.src, zp.size, zp.dst, zp.cap, execute != 0,
+                                                  lit_base ? lit_base + zp.lit_off : nullptr, zp.lit_stride, L, &total, &need,
+                                                  s3s_zstd::SkipCursor{have ? frames + sp[p].frame_base : nullptr, have ? nframes[p] : 0, 0}, &blocks,
+                                                  s3s_zstd::SkipCursor{frames2 + sp2[p].frame_base, nframes2[p], 0}, &blocks2);
+    } else if (kSkip)
       rc = s3s_zstd::decode_partition<true>(w[wave], lp[wave], zp.src, zp.size, zp.dst, zp.cap, execute != 0,
                                             lit_base ? lit_base + zp.lit_off : nullptr, zp.lit_stride, L, &total, &need,
                                             s3s_zstd::SkipCursor{frames + sp[p].frame_base, nframes[p], 0}, &blocks);
@@ -118,6 +135,7 @@ __device__ __forceinline__ void zstd_partitions_body(const ZPart* __restrict__ p
     r.pad = 0;
     res[p] = r;
     if (kSkip && blocks > 0 && rc == s3s_zstd::ZS_OK) atomicAdd(&ctrl->blocks_done, blocks);
+    if (kStaged && blocks2 > 0 && rc == s3s_zstd::ZS_OK) atomicAdd(staged_done, blocks2);
   }
 }
 #endif

@@ -27,11 +27,14 @@
 #define ZS_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
 // every lane holds the same value: say so (the value moves to a scalar register, what depends on it runs on the scalar unit)
 #define ZS_UNI32(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+// lane k's value to every lane (k is the same in every lane)
+#define ZS_BCAST32(x, k) ((uint32_t)__builtin_amdgcn_readlane((int)(x), (int)(k)))
 #else
 #define ZS_HD static inline
 #define ZS_RARE static
 #define ZS_FENCE() ((void)0)
 #define ZS_UNI32(x) ((uint32_t)(x))
+#define ZS_BCAST32(x, k) ((uint32_t)(x))
 #endif
 
 #ifdef ZS_TRACE  // host debugging only: which check refused the stream
@@ -1473,11 +1476,13 @@ struct SkipCursor {
 };
 
 // All frames of one partition (concatenated streams of a multi-spill map task).  *total = decoded bytes.  kSkip: frames that
-// the block path completed (sc) are stepped over, *blocks_done counts their blocks.
-template <bool kSkip = false>
+// the block path completed (sc) are stepped over, *blocks_done counts their blocks.  kStaged: the same for the frames the
+// staged path completed (ss, *staged_done) - its list starts where the block path's ends.
+template <bool kSkip = false, bool kStaged = false>
 ZS_HD int decode_partition(Work& w, LitPipe& lp, const uint8_t* src, int64_t size, uint8_t* dst, int64_t cap, bool execute,
                            uint8_t* lit_buf, int64_t lit_stride, Lanes L, int64_t* total, int64_t* lit_need = nullptr,
-                           SkipCursor sc = SkipCursor{nullptr, 0, 0}, int32_t* blocks_done = nullptr) {
+                           SkipCursor sc = SkipCursor{nullptr, 0, 0}, int32_t* blocks_done = nullptr,
+                           SkipCursor ss = SkipCursor{nullptr, 0, 0}, int32_t* staged_done = nullptr) {
   int64_t ip = 0, op = 0, need = 0;
   int32_t hblock = 0;
   while (ip < size) {
@@ -1487,6 +1492,15 @@ ZS_HD int decode_partition(Work& w, LitPipe& lp, const uint8_t* src, int64_t siz
         ip += f.consumed;
         op += f.fcs;
         *blocks_done += f.n_blocks;
+        continue;
+      }
+    }
+    if (kStaged && ss.at < ss.n && ss.f[ss.at].src_off == ip) {
+      const FrameEnt f = ss.f[ss.at++];
+      if (frame_complete(f)) {
+        ip += f.consumed;
+        op += f.fcs;
+        *staged_done += f.n_blocks;
         continue;
       }
     }
@@ -1502,6 +1516,596 @@ ZS_HD int decode_partition(Work& w, LitPipe& lp, const uint8_t* src, int64_t siz
   if (lit_need) *lit_need = need;
   return ZS_OK;
 }
+
+// ---- frames with history, in stages -----------------------------------------------------------------------------------
+// Within a frame only two things depend on what came before: the repeat-offset history and the bytes a match copies.  The
+// Huffman literals and the FSE sequence fields of a block lean on earlier blocks only through Treeless literals and Repeat_Mode
+// tables, and which block defined those follows from the headers.  So the stages are
+//   scan      (staged_scan_partition) frame and block headers of a run of eligible frames: a table of blocks, each with its
+//             slices of the literal and record staging and the blocks that defined its tree and tables;
+//   entropy   (staged_block_literals, staged_block_sequences) any block, any order: Huffman literals into the block's staging
+//             slice, one SeqRec per sequence, the block's decoded length;
+//   place     (staged_place_partition) prefix sums of the decoded lengths: where every block and frame lands;
+//   copy      (staged_block_copy) any block, any order: Raw and RLE blocks, and the literal runs of compressed blocks;
+//   execute   (staged_execute_frame) per frame, in order: repeat offsets resolved, match sources checked, matches copied;
+// and decode_partition<.., true> behind them steps over the frames that completed and decodes every other one as ever.  A frame
+// that any stage does not finish cleanly is flagged dependent - that is all a failure here ever does.
+struct StagedBlock {     // one block of a frame the staged path took
+  int64_t src_off;       // its 3-byte header, from the partition's first byte
+  int64_t lit_off;       // its Huffman literals in the literal staging (bytes)
+  int64_t rec_off;       // its first record in the record staging
+  int64_t out_off;       // (place) its first output byte, from the partition's first output byte
+  int32_t bsize, type;   // Block_Size, Block_Type (0 raw, 1 RLE, 2 compressed)
+  int32_t nseq, regen;   // Number_of_Sequences, regenerated size of the literals
+  int32_t ltype;         // Literals_Block_Type
+  int32_t def_huf;       // the block (index into the table) whose tree the literals use: itself, or an earlier one (Treeless); -1 none
+  int32_t def_ll, def_of, def_ml;  // the same per sequence table (Repeat_Mode)
+  int32_t frame;         // its FrameEnt
+  int32_t out_len;       // (scan) the bytes a Raw / RLE block decodes to; a compressed block's length is the entropy stage's
+                         // and lives in an array of its own beside the table (comp_len), so that no stage writes an entry of
+                         // this table while another job of the same stage reads it
+  int32_t pad;
+};
+struct SeqRec {          // one sequence, as the entropy stage leaves it: no history needed
+  uint32_t off;          // the raw Offset_Value (1..3: repeat codes)
+  uint32_t ml;           // match length
+  uint32_t reach;        // bytes of the block in front of the match (all literals and matches before it)
+  uint32_t lit_end;      // literals of the block used up to and including this sequence's run
+};
+struct StagedSums {
+  int32_t n_blocks;
+  int64_t lit_bytes, n_recs, consumed;
+};
+constexpr int32_t kStagedMaxFrameBlocks = 1 << 24;
+
+// Sequences section header at b[0, bend): Number_of_Sequences and, when that is not 0, the modes byte (RFC 8878 3.1.1.3.2.1).
+ZS_HD int sequences_header(const uint8_t* b, const uint8_t* bend, int64_t* nseq_out, int* modes_out, const uint8_t** after) {
+  if (b >= bend) return ZS_FAIL();
+  int64_t nseq = b[0];
+  if (nseq < 128) {
+    b += 1;
+  } else if (nseq < 255) {
+    if (b + 2 > bend) return ZS_FAIL();
+    nseq = ((nseq - 128) << 8) + b[1];
+    b += 2;
+  } else {
+    if (b + 3 > bend) return ZS_FAIL();
+    nseq = (int64_t)b[1] + ((int64_t)b[2] << 8) + 0x7F00;
+    b += 3;
+  }
+  int modes = 0;
+  if (nseq > 0) {
+    if (b >= bend) return ZS_FAIL();
+    modes = b[0];
+    b += 1;
+    if (modes & 3) return ZS_FAIL();
+  }
+  *nseq_out = nseq;
+  *modes_out = modes;
+  *after = b;
+  return ZS_OK;
+}
+
+// The blocks of the frame at src[0, size) (size: to the end of the partition), from headers alone: block header, literals
+// section header, sequences section header - no table description is parsed.  emit(k, block) gets every block with positions
+// relative to the frame (source offset, staging offsets, defining blocks as indices into the frame).  False: not a frame for
+// the staged path (headers that do not add up, a Repeat or Treeless with nothing in front, a regenerated size above the bound) -
+// the serial decoder names the error.
+template <class Emit>
+ZS_HD bool staged_walk_frame(const uint8_t* src, int64_t size, const FrameHdr& fh, Emit emit, StagedSums* sums) {
+  int64_t ip = fh.bytes, lit = 0, recs = 0;
+  int32_t k = 0, huf = -1, dl = -1, dof = -1, dm = -1;
+  for (;;) {
+    if (ip + 3 > size) return false;
+    const uint32_t bh = rd_le(src + ip, 3);
+    const int last = (int)(bh & 1), type = (int)((bh >> 1) & 3);
+    const int64_t bsize = bh >> 3;
+    if (type == 3 || bsize > kMaxBlock) return false;
+    const int64_t stored = type == 1 ? 1 : bsize;
+    if (ip + 3 + stored > size) return false;
+    StagedBlock sb;
+    sb.src_off = ip;
+    sb.lit_off = lit;
+    sb.rec_off = recs;
+    sb.out_off = 0;
+    sb.bsize = (int32_t)bsize;
+    sb.type = type;
+    sb.nseq = sb.regen = sb.ltype = 0;
+    sb.def_huf = sb.def_ll = sb.def_of = sb.def_ml = -1;
+    sb.frame = 0;
+    sb.out_len = type < 2 ? (int32_t)bsize : 0;
+    sb.pad = 0;
+    if (type == 2) {
+      if (bsize < 2) return false;
+      const uint8_t* b = src + ip + 3;
+      const uint8_t* const bend = b + bsize;
+      LitHdr lh;
+      if (literals_header(b, bsize, &lh) != ZS_OK) return false;
+      // the staging slice is sized by a header a hostile writer controls: the bound of the single pass's literal scratch
+      // (literals_header itself refuses more than 8 literals per compressed byte)
+      if (lh.ltype >= 2 && lh.regen > 8 * lh.lcomp + 256) return false;
+      sb.ltype = lh.ltype;
+      sb.regen = (int32_t)lh.regen;
+      if (lh.ltype == 2) huf = k;
+      if (lh.ltype >= 2) {
+        if (huf < 0) return false;  // treeless with nothing in front
+        sb.def_huf = huf;
+        lit += (lh.regen + 15) & ~(int64_t)15;
+      }
+      b += lh.lh + (lh.ltype == 0 ? lh.regen : lh.ltype == 1 ? 1 : lh.lcomp);
+      int64_t nseq;
+      int modes;
+      const uint8_t* after;
+      if (sequences_header(b, bend, &nseq, &modes, &after) != ZS_OK) return false;
+      sb.nseq = (int32_t)nseq;
+      if (nseq > 0) {  // (decode_frame's rule: a block with sequences defines every table it does not repeat)
+        if (((modes >> 6) & 3) != 3) dl = k;
+        if (((modes >> 4) & 3) != 3) dof = k;
+        if (((modes >> 2) & 3) != 3) dm = k;
+        if (dl < 0 || dof < 0 || dm < 0) return false;  // Repeat_Mode with nothing in front
+        sb.def_ll = dl;
+        sb.def_of = dof;
+        sb.def_ml = dm;
+        recs += nseq;
+      }
+    }
+    emit(k, sb);
+    k++;
+    ip += 3 + stored;
+    if (last) break;
+    if (k >= kStagedMaxFrameBlocks) return false;
+  }
+  sums->n_blocks = k;
+  sums->lit_bytes = lit;
+  sums->n_recs = recs;
+  sums->consumed = ip;
+  return true;
+}
+
+// May this frame be tried, from its header: no dictionary id field, no content checksum, not skippable; with or without a
+// content size, any window.  (Two blocks at least: the walk counts them.)
+ZS_HD bool staged_candidate(const FrameHdr& fh) { return !fh.skippable && !fh.has_did && !fh.has_check; }
+
+// The run of frames the staged path takes in one partition, from src + ip0 on (ip0 / op0: where the block path of 6j stopped
+// claiming frames, 0 / 0 without it): frames[0, return value) and block_base[] beside it (a frame's first entry of `tab`).
+// reserve(which, n): the first of n entries of the block table (0), bytes of the literal staging (1), records (2), or -1 - the
+// counters never pass their tables' sizes.  The walk stops at the first frame it cannot take; what lies behind is the serial
+// decoder's.  Output positions are not known here (no content size): frames[0].out_off carries op0 to staged_place_partition.
+template <class Reserve>
+ZS_HD int32_t staged_scan_partition(const uint8_t* src, int64_t size, int32_t part, int64_t ip0, int64_t op0, FrameEnt* frames,
+                                    int32_t* block_base, int32_t frame_cap, int32_t frame_id0, StagedBlock* tab, Reserve reserve) {
+  int64_t ip = ip0;
+  int32_t nf = 0;
+  while (ip < size && nf < frame_cap) {
+    FrameHdr fh;
+    if (frame_header(src + ip, size - ip, &fh) != ZS_OK) break;
+    if (!staged_candidate(fh)) break;
+    StagedSums s;
+    if (!staged_walk_frame(src + ip, size - ip, fh, [](int32_t, const StagedBlock&) {}, &s)) break;
+    if (s.n_blocks < 2) break;
+    // (the block table last: entries handed out are entries filled - what the staging pools handed out in vain is only lost)
+    const int64_t lb = reserve(1, s.lit_bytes);
+    if (lb < 0) break;
+    const int64_t rb = reserve(2, s.n_recs);
+    if (rb < 0) break;
+    const int64_t bb = reserve(0, (int64_t)s.n_blocks);
+    if (bb < 0) break;
+    const int32_t fid = frame_id0 + nf;
+    StagedSums s2;
+    staged_walk_frame(src + ip, size - ip, fh,
+                      [&](int32_t k, const StagedBlock& in) {
+                        StagedBlock sb = in;
+                        sb.src_off += ip;
+                        sb.lit_off += lb;
+                        sb.rec_off += rb;
+                        if (sb.def_huf >= 0) sb.def_huf += (int32_t)bb;
+                        if (sb.def_ll >= 0) sb.def_ll += (int32_t)bb;
+                        if (sb.def_of >= 0) sb.def_of += (int32_t)bb;
+                        if (sb.def_ml >= 0) sb.def_ml += (int32_t)bb;
+                        sb.frame = fid;
+                        if (k < s.n_blocks) tab[bb + k] = sb;
+                      },
+                      &s2);
+    FrameEnt f;
+    f.src_off = ip;
+    f.consumed = s.consumed;
+    f.out_off = nf == 0 ? op0 : 0;
+    f.fcs = fh.fcs;  // (declared, -1 when absent: place holds the decoded length against it and then stores that length here)
+    f.n_blocks = s.n_blocks;
+    f.part = part;
+    f.done = 0;
+    f.dependent = 0;
+    block_base[nf] = (int32_t)bb;
+    frames[nf++] = f;
+    ip += s.consumed;
+  }
+  return nf;
+}
+
+// ---- entropy stage --------------------------------------------------------------------------------------------------------------------
+struct SeqWork {  // the sequence tables of one block (LDS on the device)
+  uint32_t ll[1 << kLLLogMax], ml[1 << kMLLogMax], of[1 << kOFLogMax];
+  uint32_t llv[1 << kLLLogMax], mlv[1 << kMLLogMax];
+  int16_t norm[64];
+  uint16_t next[64];
+  int32_t ll_log, ml_log, of_log;
+};
+
+// literals section header, then sequences section header of the compressed block body b[0, bsize)
+struct SeqSect {
+  LitHdr lh;
+  const uint8_t* desc;   // behind the modes byte: the table descriptions, then the bit stream
+  const uint8_t* bend;
+  int64_t nseq;
+  int modes;
+};
+ZS_HD int staged_section(const uint8_t* b, int64_t bsize, SeqSect* s) {
+  if (bsize < 2 || bsize > kMaxBlock) return ZS_FAIL();
+  const int rc = literals_header(b, bsize, &s->lh);
+  if (rc != ZS_OK) return rc;
+  s->bend = b + bsize;
+  const uint8_t* q = b + s->lh.lh + (s->lh.ltype == 0 ? s->lh.regen : s->lh.ltype == 1 ? 1 : s->lh.lcomp);
+  return sequences_header(q, s->bend, &s->nseq, &s->modes, &s->desc);
+}
+// Table t (0 LL, 1 OF, 2 ML) in mode 0 / 1 / 2 from its description at b (advanced over it); build = false only steps over it.
+ZS_HD int staged_table(SeqWork& w, int t, int mode, const uint8_t*& b, const uint8_t* bend, bool build) {
+  uint32_t* tab = t == 0 ? w.ll : t == 1 ? w.of : w.ml;
+  int32_t& tlog = t == 0 ? w.ll_log : t == 1 ? w.of_log : w.ml_log;
+  const int max_sym = t == 0 ? 35 : t == 1 ? 31 : 52, max_log = t == 0 ? kLLLogMax : t == 1 ? kOFLogMax : kMLLogMax;
+  if (mode == 0) {
+    if (build) {
+      int log;
+      const int ms = default_norm(t, w.norm, &log);
+      if (build_fse(tab, w.norm, ms, log, w.next) != ZS_OK) return ZS_FAIL();
+      tlog = log;
+    }
+  } else if (mode == 1) {
+    if (b >= bend) return ZS_FAIL();
+    if (b[0] > max_sym) return ZS_FAIL();
+    if (build) {
+      build_rle(tab, b[0]);
+      tlog = 0;
+    }
+    b += 1;
+  } else if (mode == 2) {
+    int ms, log;
+    const int used = read_ncount(w.norm, max_sym, max_log, b, bend - b, &ms, &log);
+    if (used < 0) return used;
+    if (build) {
+      if (build_fse(tab, w.norm, ms, log, w.next) != ZS_OK) return ZS_FAIL();
+      tlog = log;
+    }
+    b += used;
+  } else {
+    return ZS_FAIL();
+  }
+  return ZS_OK;
+}
+// Table t as block `def` of the table defined it: that block's section is parsed again up to the description.  Whether that
+// block itself decodes is not asked; a description that does not parse fails THIS block.
+ZS_HD int staged_table_of(SeqWork& w, int t, const uint8_t* psrc, const StagedBlock& def) {
+  if (def.type != 2) return ZS_FAIL();
+  SeqSect s;
+  const int rc = staged_section(psrc + def.src_off + 3, def.bsize, &s);
+  if (rc != ZS_OK) return rc;
+  if (s.nseq == 0) return ZS_FAIL();
+  const uint8_t* b = s.desc;
+  for (int u = 0; u <= t; u++) {
+    const int mode = (s.modes >> (6 - 2 * u)) & 3;
+    if (u == t) return staged_table(w, t, mode, b, s.bend, true);  // (mode 3 here: not the defining block after all)
+    if (mode != 3) {
+      const int r2 = staged_table(w, u, mode, b, s.bend, false);
+      if (r2 != ZS_OK) return r2;
+    }
+  }
+  return ZS_FAIL();
+}
+
+// The Huffman-coded literals of block bi into its slice of the literal staging.  Raw and RLE literals are not staged.
+ZS_HD int staged_block_literals(HufWork& h, const uint8_t* psrc, const StagedBlock* tab, int32_t bi, uint8_t* lit_pool, int64_t lit_cap,
+                                Lanes L) {
+  const StagedBlock blk = tab[bi];
+  if (blk.type != 2 || blk.ltype < 2) return ZS_OK;
+  const uint8_t* b = psrc + blk.src_off + 3;
+  LitHdr lh;
+  const int rc = literals_header(b, blk.bsize, &lh);
+  if (rc != ZS_OK) return rc;
+  if (lh.ltype != blk.ltype || lh.regen != blk.regen) return ZS_FAIL();
+  if (blk.lit_off < 0 || blk.lit_off + lh.regen > lit_cap) return ZS_FAIL();
+  h.have_huf = 0;
+  if (lh.ltype == 3) {  // the tree of the block that defined it, from that block's description
+    const int32_t d = blk.def_huf;
+    if (d < 0 || d >= bi) return ZS_FAIL();
+    const StagedBlock db = tab[d];
+    if (db.type != 2 || db.frame != blk.frame) return ZS_FAIL();
+    const uint8_t* q = psrc + db.src_off + 3;
+    LitHdr dlh;
+    const int r2 = literals_header(q, db.bsize, &dlh);
+    if (r2 != ZS_OK) return r2;
+    if (dlh.ltype != 2) return ZS_FAIL();
+    const int used = read_huf_table(h, q + dlh.lh, dlh.lcomp);
+    if (used < 0) return used;
+    ZS_FENCE();
+  }
+  return block_literals(h, lh, b + lh.lh, lh.lcomp, lit_pool + blk.lit_off, L);
+}
+
+// The sequences of block bi: one record each, and the block's decoded length.  decode_frame's checks that need no history: the
+// stream is consumed exactly, literals used <= regenerated size, at most kMaxBlock bytes, offset code <= 31.
+ZS_HD int staged_block_sequences(SeqWork& w, const uint8_t* psrc, const StagedBlock* tab, int32_t bi, SeqRec* rec_pool, int64_t rec_cap,
+                                 int32_t* out_len, Lanes L) {
+  const StagedBlock blk = tab[bi];
+  if (blk.type != 2) return ZS_OK;  // (Raw / RLE: the scan knew their length)
+  SeqSect s;
+  {
+    const int rc = staged_section(psrc + blk.src_off + 3, blk.bsize, &s);
+    if (rc != ZS_OK) return rc;
+  }
+  const int64_t nseq = s.nseq;
+  const uint32_t regen32 = (uint32_t)s.lh.regen;
+  if (nseq != blk.nseq || s.lh.regen != blk.regen) return ZS_FAIL();
+  uint32_t bout = 0, lit_pos = 0;
+  if (nseq == 0) {
+    if (s.desc != s.bend) return ZS_FAIL();
+  } else {
+    if (blk.rec_off < 0 || blk.rec_off + nseq > rec_cap) return ZS_FAIL();
+    SeqRec* const recs = rec_pool + blk.rec_off;
+    const uint8_t* b = s.desc;
+    for (int t = 0; t < 3; t++) {  // LL, OF, ML
+      const int mode = (s.modes >> (6 - 2 * t)) & 3;
+      if (mode != 3) {
+        const int rc = staged_table(w, t, mode, b, s.bend, true);
+        if (rc != ZS_OK) return rc;
+      } else {
+        const int32_t d = t == 0 ? blk.def_ll : t == 1 ? blk.def_of : blk.def_ml;
+        if (d < 0 || d >= bi) return ZS_FAIL();
+        const StagedBlock db = tab[d];
+        if (db.frame != blk.frame) return ZS_FAIL();
+        const int rc = staged_table_of(w, t, psrc, db);
+        if (rc != ZS_OK) return rc;
+      }
+    }
+    for (int u = L.lane; u < (1 << w.ll_log); u += L.n) {
+      const int c = (int)(w.ll[u] >> 24);
+      w.llv[u] = ll_base(c) | ((uint32_t)ll_bits(c) << 24);
+    }
+    for (int u = L.lane; u < (1 << w.ml_log); u += L.n) {
+      const int c = (int)(w.ml[u] >> 24);
+      w.mlv[u] = ml_base(c) | ((uint32_t)ml_bits(c) << 24);
+    }
+    ZS_FENCE();
+    BitR r;
+    if (!bitr_init(r, b, s.bend - b)) return ZS_FAIL();
+    uint32_t sl = bitr_read(r, w.ll_log), so = bitr_read(r, w.of_log), sm = bitr_read(r, w.ml_log);
+    if (r.pos < 0) return ZS_FAIL();
+    for (int64_t i = 0; i < nseq; i++) {
+      const uint32_t el = ZS_UNI32(w.ll[sl]), eo = ZS_UNI32(w.of[so]), em = ZS_UNI32(w.ml[sm]);
+      const uint32_t vl = ZS_UNI32(w.llv[sl]), vm = ZS_UNI32(w.mlv[sm]);
+      const int co = (int)(eo >> 24);
+      if (co > 31) return ZS_FAIL();
+      uint32_t ov, mlen, llen;
+      // (the field extraction of decode_frame's sequence loop: all fields of a sequence from one window where they fit)
+      const int bm = (int)(vm >> 24), bl = (int)(vl >> 24);
+      const bool more = i + 1 < nseq;
+      const int nl = more ? (int)((el >> 16) & 0xff) : 0, nm = more ? (int)((em >> 16) & 0xff) : 0, no = more ? (int)((eo >> 16) & 0xff) : 0;
+      const int nb = co + bm + bl + nl + nm + no;
+      if (nb <= 57) {
+        if (!(r.pos - nb >= r.cbase && r.pos <= r.cbase + 64)) {
+          const int32_t top = (r.pos - 1) >> 3;
+          r.cbase = (top - 7) * 8;
+          r.cache = load_bits64(r.p, r.size, top - 7);
+#ifdef S3S_ZSTD_DEVICE
+          r.cache = (uint64_t)ZS_UNI32((uint32_t)r.cache) | ((uint64_t)ZS_UNI32((uint32_t)(r.cache >> 32)) << 32);
+#endif
+        }
+        const int sh = r.pos - nb - r.cbase;
+        const uint64_t bits = sh < 64 ? r.cache >> sh : 0;
+        int rem = nb;
+        auto take = [&](int n) -> uint32_t {
+          rem -= n;
+          return (uint32_t)(bits >> rem) & ((1u << n) - 1u);
+        };
+        ov = take(co);
+        mlen = (vm & 0xFFFFFFu) + take(bm);
+        llen = (vl & 0xFFFFFFu) + take(bl);
+        sl = (el & 0xFFFFu) + take(nl);
+        sm = (em & 0xFFFFu) + take(nm);
+        so = (eo & 0xFFFFu) + take(no);
+        r.pos -= nb;
+      } else {
+        if (co > 24) {
+          const uint32_t hi = bitr_read(r, co - 16);
+          ov = (hi << 16) | bitr_read(r, 16);
+        } else {
+          ov = bitr_read(r, co);
+        }
+        mlen = (vm & 0xFFFFFFu) + bitr_read(r, bm);
+        llen = (vl & 0xFFFFFFu) + bitr_read(r, bl);
+        if (more) {
+          sl = (el & 0xFFFFu) + bitr_read(r, nl);
+          sm = (em & 0xFFFFu) + bitr_read(r, nm);
+          so = (eo & 0xFFFFu) + bitr_read(r, no);
+        }
+      }
+      const uint32_t oval = (1u << co) + ov;
+      const uint32_t reach = bout + llen, nbout = reach + mlen;
+      if (r.pos < 0 || lit_pos + llen > regen32 || nbout > (uint32_t)kMaxBlock) return ZS_FAIL();
+      lit_pos += llen;
+      bout = nbout;
+      if (L.lane == 0) {
+        SeqRec q;
+        q.off = oval;
+        q.ml = mlen;
+        q.reach = reach;
+        q.lit_end = lit_pos;
+        recs[i] = q;
+      }
+    }
+    if (r.pos != 0) return ZS_FAIL();  // the sequence stream must be consumed exactly
+  }
+  bout += regen32 - lit_pos;  // literals behind the last sequence
+  if (bout > (uint32_t)kMaxBlock) return ZS_FAIL();
+  *out_len = (int32_t)bout;
+  return ZS_OK;
+}
+
+// ---- place ------------------------------------------------------------------------------------------------------------------------------
+// Prefix sums of the decoded lengths: out_off of every block and frame of one partition's run, inside cap.  A frame that the
+// entropy stage flagged has no known length: it and everything behind it is the serial decoder's; so is whatever would pass
+// the partition's capacity (the serial decoder then answers ZS_CAPACITY), and a frame whose header states a content size other
+// than the length its blocks decode to.  On entry a frame's fcs is the stated size (-1: none), on exit its decoded length.
+// comp_len[b]: the decoded length of compressed block b of the table, as the entropy stage left it.
+ZS_HD void staged_place_partition(FrameEnt* frames, const int32_t* block_base, int32_t nf, StagedBlock* tab, const int32_t* comp_len,
+                                  int64_t cap, Lanes L) {
+  if (nf <= 0) return;
+  int64_t op = frames[0].out_off;
+  bool lost = false;
+  for (int32_t f = 0; f < nf; f++) {
+    const FrameEnt fe = frames[f];
+    if (lost || fe.dependent) {
+      lost = true;
+      if (L.lane == 0) frames[f].dependent = 1;
+      continue;
+    }
+    StagedBlock* const bt = tab + block_base[f];
+    const int32_t* const cl = comp_len + block_base[f];
+    int64_t flen = 0;
+    for (int32_t j0 = 0; j0 < fe.n_blocks; j0 += L.n) {
+      const int32_t j = j0 + L.lane;
+      const uint32_t mine = j < fe.n_blocks ? (uint32_t)(bt[j].type == 2 ? cl[j] : bt[j].out_len) : 0u;
+      const int32_t cnt = fe.n_blocks - j0 < L.n ? fe.n_blocks - j0 : L.n;
+      uint32_t run = 0, excl = 0;
+      for (int32_t k = 0; k < cnt; k++) {
+        if (k == L.lane) excl = run;
+        run += ZS_BCAST32(mine, k);
+      }
+      if (j < fe.n_blocks) bt[j].out_off = op + flen + (int64_t)excl;
+      flen += (int64_t)run;
+    }
+    // (decode_frame's last check: a stated Frame_Content_Size that the blocks do not add up to is the serial decoder's error)
+    if (flen > cap - op || (fe.fcs >= 0 && fe.fcs != flen)) {
+      lost = true;
+      if (L.lane == 0) frames[f].dependent = 1;
+      continue;
+    }
+    if (L.lane == 0) {
+      frames[f].out_off = op;
+      frames[f].fcs = flen;
+    }
+    op += flen;
+  }
+}
+
+// ---- copy -------------------------------------------------------------------------------------------------------------------------------
+// What of a block's output needs nothing in front of it: a Raw or RLE block as a whole, the literal runs of a compressed block
+// (their positions are in the records) and the literals behind its last sequence.  pdst: the partition's first output byte.
+ZS_HD void staged_block_copy(const uint8_t* psrc, uint8_t* pdst, const StagedBlock& blk, const SeqRec* rec_pool, const uint8_t* lit_pool,
+                             Lanes L) {
+  uint8_t* const o = pdst + blk.out_off;
+  const uint8_t* const b = psrc + blk.src_off + 3;
+  if (blk.type == 0) {
+    for (int32_t i = L.lane; i < blk.bsize; i += L.n) o[i] = b[i];
+    return;
+  }
+  if (blk.type == 1) {
+    const uint8_t v = b[0];
+    for (int32_t i = L.lane; i < blk.bsize; i += L.n) o[i] = v;
+    return;
+  }
+  LitHdr lh;
+  if (literals_header(b, blk.bsize, &lh) != ZS_OK) return;  // (the scan and the entropy stage read the same header)
+  const uint8_t* const lit = lh.ltype == 0 ? b + lh.lh : lh.ltype == 1 ? nullptr : lit_pool + blk.lit_off;
+  const uint8_t fillv = lh.ltype == 1 ? b[lh.lh] : 0;
+  const SeqRec* const recs = rec_pool + blk.rec_off;
+  const int32_t nseq = blk.nseq;
+  for (int32_t j = L.lane; j < nseq; j += L.n) {
+    const SeqRec r = recs[j];
+    uint32_t start = 0, ls = 0;
+    if (j > 0) {
+      const SeqRec pr = recs[j - 1];
+      start = pr.reach + pr.ml;
+      ls = pr.lit_end;
+    }
+    const uint32_t n = r.reach - start;
+    if (lit) for (uint32_t i = 0; i < n; i++) o[start + i] = lit[ls + i];
+    else for (uint32_t i = 0; i < n; i++) o[start + i] = fillv;
+  }
+  uint32_t start = 0, ls = 0;
+  if (nseq > 0) {
+    const SeqRec pr = recs[nseq - 1];
+    start = pr.reach + pr.ml;
+    ls = pr.lit_end;
+  }
+  const uint32_t rest = (uint32_t)blk.regen - ls;
+  if (lit) for (uint32_t i = (uint32_t)L.lane; i < rest; i += (uint32_t)L.n) o[start + i] = lit[ls + i];
+  else for (uint32_t i = (uint32_t)L.lane; i < rest; i += (uint32_t)L.n) o[start + i] = fillv;
+}
+
+// ---- execute ----------------------------------------------------------------------------------------------------------------------------
+// One frame, its blocks in order: the repeat-offset history by decode_frame's rule (rep0 - 1 and offset 0 included), every match
+// source checked against the bytes the frame has produced so far, the matches copied.  Literals are in place already (an
+// earlier kernel on the device), so a match source must only wait for the MATCHES written here: dirty = the lowest frame
+// position written since the last fence.  fdst: the frame's first output byte.
+ZS_HD int staged_execute_frame(const FrameEnt& fe, const StagedBlock* bt, const SeqRec* rec_pool, uint8_t* fdst, Lanes L) {
+  uint32_t rep0 = 1, rep1 = 4, rep2 = 8;
+  const int64_t kClean = (int64_t)1 << 62;
+  int64_t dirty = kClean;
+  for (int32_t k = 0; k < fe.n_blocks; k++) {
+    const StagedBlock blk = bt[k];
+    if (blk.type != 2 || blk.nseq == 0) continue;
+    const int64_t fpos = blk.out_off - fe.out_off;  // bytes of the frame in front of the block
+    const SeqRec* const recs = rec_pool + blk.rec_off;
+    uint32_t prev_end = 0;
+    for (int32_t j0 = 0; j0 < blk.nseq; j0 += L.n) {
+      const int32_t j = j0 + L.lane;
+      SeqRec mine;
+      mine.off = mine.ml = mine.reach = mine.lit_end = 0;
+      if (j < blk.nseq) mine = recs[j];
+      const int32_t cnt = blk.nseq - j0 < L.n ? blk.nseq - j0 : L.n;
+      for (int32_t t = 0; t < cnt; t++) {
+        const uint32_t oval = ZS_BCAST32(mine.off, t), mlen = ZS_BCAST32(mine.ml, t), reach = ZS_BCAST32(mine.reach, t);
+        const uint32_t llen = reach - prev_end;
+        prev_end = reach + mlen;
+        const bool is_rep = oval <= 3;
+        const uint32_t idx = oval - 1 + (llen == 0 ? 1u : 0u);
+        uint32_t rv = rep0;
+        rv = idx == 1 ? rep1 : rv;
+        rv = idx == 2 ? rep2 : rv;
+        rv = idx == 3 ? rep0 - 1 : rv;
+        const uint32_t offset = is_rep ? rv : oval - 3;
+        const bool change = !is_rep || idx != 0, deep = !is_rep || idx >= 2;
+        rep2 = deep ? rep1 : rep2;
+        rep1 = change ? rep0 : rep1;
+        rep0 = change ? offset : rep0;
+        const int64_t pos = fpos + (int64_t)reach;
+        if (offset == 0 || (int64_t)offset > pos) return ZS_FAIL();  // (no dictionary: history starts with the frame)
+        const int64_t from = pos - (int64_t)offset;
+        const int64_t src_end = from + (int64_t)(mlen < offset ? mlen : offset);
+        if (src_end > dirty) {
+          ZS_FENCE();
+          dirty = kClean;
+        }
+        uint8_t* const o = fdst + pos;
+        const uint8_t* const pat = fdst + from;
+        if (offset >= mlen) {
+          for (uint32_t i = (uint32_t)L.lane; i < mlen; i += (uint32_t)L.n) o[i] = pat[i];
+        } else {
+          for (uint32_t i = (uint32_t)L.lane; i < mlen; i += (uint32_t)L.n) o[i] = pat[i % offset];
+        }
+        dirty = pos < dirty ? pos : dirty;
+      }
+    }
+  }
+  return ZS_OK;
+}
+
+// The call's staging, from the compressed bytes it holds (the only size the host knows): tables the scan hands out of, never
+// trusted to be enough - a frame that does not fit stays with the serial decoder.  20 bytes per compressed byte and ~100 KiB
+// (measured on libzstd level-1 frames: 0.1 - 0.8 sequences and 0.4 - 1.3 Huffman literals per compressed byte).
+constexpr int64_t staged_block_cap(int64_t comp_bytes) { return comp_bytes / 32 + 64; }     // entries of the block table (64 bytes each)
+constexpr int64_t staged_lit_cap(int64_t comp_bytes) { return 2 * comp_bytes + 65536; }    // bytes of Huffman literals
+constexpr int64_t staged_rec_cap(int64_t comp_bytes) { return comp_bytes + 2048; }         // records (16 bytes each)
+constexpr int32_t kStagedFramesPerPart = 16;  // frames of one partition the staged path takes at most (a partition has one per spill)
 
 #ifdef S3S_ZSTD_DEVICE
 // ---- the literal wavefront (device) ------------------------------------------------------------------------------------------
@@ -1523,14 +2127,22 @@ struct LitWalker {
   int64_t bsize;
 };
 // to the next Huffman-coded literals section (have = 1) or the end of the partition (done = 1)
-template <bool kSkip = false>
-ZS_HD void walker_advance(LitWalker& k, LitPipe& lp, Lanes L, SkipCursor* sc = nullptr) {
+template <bool kSkip = false, bool kStaged = false>
+ZS_HD void walker_advance(LitWalker& k, LitPipe& lp, Lanes L, SkipCursor* sc = nullptr, SkipCursor* ss = nullptr) {
   for (;;) {
     if (!k.in_frame) {
       if (k.ip >= k.size) { k.done = 1; return; }
       if (kSkip && sc->at < sc->n && sc->f[sc->at].src_off == k.ip) {  // (the same decision as decode_partition's, from the same memory)
         const FrameEnt f = sc->f[sc->at];
         sc->at++;
+        if (frame_complete(f)) {
+          k.ip += f.consumed;
+          continue;
+        }
+      }
+      if (kStaged && ss->at < ss->n && ss->f[ss->at].src_off == k.ip) {  // (and of the staged path's list)
+        const FrameEnt f = ss->f[ss->at];
+        ss->at++;
         if (frame_complete(f)) {
           k.ip += f.consumed;
           continue;
@@ -1574,8 +2186,8 @@ ZS_HD void walker_advance(LitWalker& k, LitPipe& lp, Lanes L, SkipCursor* sc = n
   k.done = 1;
 }
 // n_parts (1 or 2) partitions of the workgroup: whichever has a block to regenerate and a free buffer goes next
-template <bool kSkip = false>
-ZS_HD void literal_side(LitPipe* lps, LitWalker* ks, int n_parts, Lanes L, SkipCursor* scs = nullptr) {
+template <bool kSkip = false, bool kStaged = false>
+ZS_HD void literal_side(LitPipe* lps, LitWalker* ks, int n_parts, Lanes L, SkipCursor* scs = nullptr, SkipCursor* sss = nullptr) {
   int32_t idle = 0;
   for (;;) {
     bool any = false, progressed = false;
@@ -1584,7 +2196,7 @@ ZS_HD void literal_side(LitPipe* lps, LitWalker* ks, int n_parts, Lanes L, SkipC
       LitPipe& lp = lps[t];
       if (k.done) continue;
       if (!k.have) {
-        walker_advance<kSkip>(k, lp, L, kSkip ? scs + t : nullptr);
+        walker_advance<kSkip, kStaged>(k, lp, L, kSkip ? scs + t : nullptr, kStaged ? sss + t : nullptr);
         if (k.done) continue;
       }
       any = true;

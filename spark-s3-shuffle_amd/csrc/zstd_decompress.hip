@@ -9,7 +9,7 @@
 //           by pass 1 (the largest regenerated literals section of its blocks).
 // Compression with this codec stays on the JVM: s3s_compress_* answer S3S_E_UNSUPPORTED.
 #define S3S_ZSTD_DEVICE 1
-#include "zstd_decode_blocks.h"
+#include "zstd_decode_staged.h"
 
 #include <vector>
 
@@ -63,6 +63,7 @@ static_assert(s3s_zstd::ZS_BAD == S3S_E_BAD_FRAME && s3s_zstd::ZS_CAPACITY == S3
 int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, int32_t n_ranges, bool size_only, bool* regular_end) {
   if (regular_end) *regular_end = false;  // true: every range has its own verdict (the return value is the first bad one's)
   ctx->zstd_decode_blocks = 0;
+  ctx->zstd_decode_staged_blocks = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (auto& v : ctx->stage_ms) v = 0;
   int64_t n_parts64 = 0, n_segs64 = 0;
@@ -95,7 +96,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
   auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
   const size_t o_parts = 0, o_res = al(o_parts + sizeof(ZPart) * (size_t)n_parts), o_off = al(o_res + sizeof(ZRes) * (size_t)n_parts),
                o_seg = al(o_off + 8 * ((size_t)n_parts + (size_t)n_ranges)), o_sums = al(o_seg + 4 * ((size_t)n_parts + (size_t)n_ranges)),
-               o_ctrl = al(o_sums + 8 * (size_t)n_parts), stage_total = o_ctrl + sizeof(ZBlockCtrl) + 64;
+               o_ctrl = al(o_sums + 8 * (size_t)n_parts), o_sctrl = al(o_ctrl + sizeof(ZBlockCtrl)), stage_total = o_sctrl + sizeof(ZStagedCtrl) + 64;
   int rc;
   if ((rc = ensure_stage(ctx, stage_total))) return rc;
   uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
@@ -105,6 +106,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
   int32_t* h_seg = reinterpret_cast<int32_t*>(hs + o_seg);
   int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);
   ZBlockCtrl* h_ctrl = reinterpret_cast<ZBlockCtrl*>(hs + o_ctrl);
+  ZStagedCtrl* h_sctrl = reinterpret_cast<ZStagedCtrl*>(hs + o_sctrl);
   record(ctx, 0);
   // ---- per-partition Adler32 / CRC32 over the compressed bytes (S3ChecksumValidationStream) ---------------------
   if (checksum_algo != S3S_CHECKSUM_NONE) {
@@ -215,7 +217,16 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
     // place.  plan.on = false (variant 0, or no partition large enough to hold such a frame): today's launches, nothing else.
     ZBlockPlan plan;
     if (ctx->zstd_decode_variant == 1 && (rc = zstd_blocks_launch(ctx, h_parts, dev<ZPart>(ctx, B_RANGES), n_parts, &plan))) return rc;
-    if (plan.on) {
+    // Frames with history (DESIGN.md 6k, S3S_OPT_ZSTD_DECODE_STAGED = 1): entropy per block, copies per frame, behind the block
+    // path's kernels and in front of the per-partition kernel, which then steps over the frames of both.  Its staging has the
+    // scratch budget once more, beside the scratch itself.  splan.on = false (the option is 0): the launches above and below.
+    ZStagedPlan splan;
+    if (ctx->zstd_decode_staged == 1 &&
+        (rc = zstd_staged_launch(ctx, h_parts, dev<ZPart>(ctx, B_RANGES), n_parts, plan, kScratchBudget, &splan)))
+      return rc;
+    if (splan.on) {
+      zstd_partitions_staged_launch(ctx, dev<ZPart>(ctx, B_RANGES), n_parts, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES), plan, splan);
+    } else if (plan.on) {
       zstd_partitions_skip_launch(ctx, dev<ZPart>(ctx, B_RANGES), n_parts, dev<uint8_t>(ctx, B_SLOTS), dev<ZRes>(ctx, B_FRAMES), plan);
     } else {
       hipLaunchKernelGGL(zstd_partitions_kernel, dim3((unsigned)((n_parts + 1) / 2)), dim3(kZstdThreads), 0, ctx->stream, dev<ZPart>(ctx, B_RANGES),
@@ -224,6 +235,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(h_res, ctx->buf[B_FRAMES].p, sizeof(ZRes) * (size_t)n_parts, hipMemcpyDeviceToHost, ctx->stream));
     if (plan.on) HIP_TRY(ctx, hipMemcpyAsync(h_ctrl, plan.d_ctrl, sizeof(ZBlockCtrl), hipMemcpyDeviceToHost, ctx->stream));
+    if (splan.on) HIP_TRY(ctx, hipMemcpyAsync(h_sctrl, splan.d_ctrl, sizeof(ZStagedCtrl), hipMemcpyDeviceToHost, ctx->stream));
     record(ctx, 2);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // verdicts; a partition that outgrew its guess sends the whole call to the two-pass form
@@ -262,6 +274,7 @@ int zstd_decompress_ranges(s3s_ctx* ctx, int checksum_algo, s3s_fetch_range* R, 
     }
     if (!outgrown) {
       if (plan.on) ctx->zstd_decode_blocks = h_ctrl->blocks_done;
+      if (splan.on) ctx->zstd_decode_staged_blocks = h_sctrl->blocks_done;
       std::vector<ZPiece> pcs;  // (source of an asynchronous copy: lives until the stream has been synchronised below)
       if (n_pieces > 0) {
         if ((rc = ensure(ctx, B_ZPIECES, sizeof(ZPiece) * (size_t)n_pieces))) return rc;

@@ -26,6 +26,8 @@ OPT_STREAM_CLASS = 12  # ABI 11, additive, read-only: queue pool of the context'
 OPT_IO_ENCRYPTION_KEY_BITS = 11  # ABI 11, additive, read-only: 0 / 128 / 192 / 256 - the key Codec.set_io_encryption holds
 OPT_ZSTD_DECODE_VARIANT = 13  # ABI 11, additive: 1 (default) = block-independent Zstandard frames one workgroup per block, 0 = one frame per wavefront
 OPT_ZSTD_DECODE_BLOCKS = 14  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the block path
+OPT_ZSTD_DECODE_STAGED = 15  # ABI 11, additive: 0 (default) / 1 = Zstandard frames with history across blocks decode in stages (entropy per block, copies per frame)
+OPT_ZSTD_DECODE_STAGED_BLOCKS = 16  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the staged path
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
 STATUS_NOT_RUN = -100  # per-entry status of a batch call that failed as a call before this entry had a verdict (ABI 6)
@@ -255,6 +257,11 @@ class Codec:
     def zstd_decode_blocks(self) -> int:
         """Blocks of the last Zstandard decode call whose frames completed on the block path (OPT_ZSTD_DECODE_VARIANT = 1), else 0."""
         return self.get_option(OPT_ZSTD_DECODE_BLOCKS)
+
+    @property
+    def zstd_decode_staged_blocks(self) -> int:
+        """Blocks of the last Zstandard decode call whose frames completed on the staged path (OPT_ZSTD_DECODE_STAGED = 1), else 0."""
+        return self.get_option(OPT_ZSTD_DECODE_STAGED_BLOCKS)
 
     def stage_ms(self, stage: int) -> float:
         return float(self._lib.s3s_stage_ms(self._h, stage))
