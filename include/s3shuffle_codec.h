@@ -481,8 +481,10 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          stream.  s3s_dstream_feed (host buffers) stages the window and dst_capacity bytes of output in that workspace:
  *          the caller's two sizes are the memory bound.  (A stream opened by s3s_dstream_open_encrypted holds one more
  *          window-sized buffer there during a feed: the decrypted window.)
- * Refused  at open with S3S_E_UNSUPPORTED, context intact: S3S_CODEC_ZSTD (a frame is a whole partition with history across
- *          its blocks and, from zstd-jni's streaming writer, no content size: resumable Zstandard is separate work) and, by
+ * Refused  at open with S3S_E_UNSUPPORTED, context intact: S3S_CODEC_ZSTD by s3s_dstream_open and s3s_dstream_open_encrypted (a
+ *          frame is a whole partition with history across its blocks and, from zstd-jni's streaming writer, no content size:
+ *          a Zstandard stream keeps device memory between feeds and has units of its own, both new to a caller -
+ *          s3s_dstream_open_zstd, below, is the opt-in, and callers from before it rely on this answer to fall back) and, by
  *          s3s_dstream_open, any context with IO encryption on: callers from before s3s_dstream_open_encrypted rely on that
  *          answer to fall back, and the units of an encrypted range are new to a caller (below) - s3s_dstream_open_encrypted
  *          is the opt-in.  Both keep the one-shot call.  S3S_OPT_LZ4_DECODE_VARIANT = 3 WORKS: a feed launches whichever
@@ -512,7 +514,49 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          stands follows from the position.  Between feeds the stream holds no device memory; one-shot encrypted calls on the
  *          same context may run between two feeds.
  * Result   the concatenation of all dst outputs is what s3s_decompress_range_device writes for the same range under the same
- *          key, and the final verdict falls in the same class. */
+ *          key, and the final verdict falls in the same class.
+ *
+ * Zstandard: s3s_dstream_open_zstd (ABI 11, additive: callers detect support by the symbol) takes the arguments of
+ * s3s_dstream_open without the codec, makes its checks, and window_log_max = 10 .. 27 (anything else: S3S_E_INVALID): the
+ * caller's memory promise - the stream keeps at most 1 << window_log_max bytes of history for its open frame.  (libzstd's
+ * streaming writer with an unknown source size, which is what zstd-jni's ZstdOutputStream is, writes window log 19 at level 1
+ * and 21 at level 3: read from the headers of such frames, libzstd 1.4.8.)  A context with IO encryption on is refused with
+ * S3S_E_UNSUPPORTED.  feed, feed_device, position and close work on the stream unchanged.  The contract above holds with these
+ * changes only:
+ * Units    a frame header of 6 .. 18 bytes (decodes to nothing);  a block: its 3-byte header plus Block_Size payload bytes
+ *          (1 byte for an RLE block), which decodes to at most 128 KiB;  a skippable frame of 8 + n bytes (decodes to nothing).
+ *          A partition is zero or more frames (several: multi-spill).  The position is never inside a unit.
+ * need_comp  a frame header takes two steps at most (6: the magic and the descriptor, then the header's length; a skippable
+ *          frame 6, 8, then 8 + n), a block two (3, then header plus payload) and never more than 3 + 128 KiB.
+ * need_dst a compressed block's decoded size is not in its header: a feed runs a size pass (no stores) over the blocks of its
+ *          window, like the one-shot call, cuts by dst_capacity at a block boundary, exactly, and only then decodes.
+ *          S3S_E_CAPACITY carries the exact decoded size of the first block; need_dst never exceeds 128 KiB.  Longest prefix
+ *          and progress hold as above (a unit of no output always fits).
+ * Refused  by the feed whose window shows the header, with S3S_E_UNSUPPORTED, consumed = 0, out_len = 0, not sticky (the shape
+ *          of the Snappy oversized claim): a frame with a Content_Checksum (a running XXH64 across feeds is not built), a frame
+ *          with a Dictionary_ID field, a frame whose Window_Size exceeds 1 << window_log_max (a single-segment frame's is its
+ *          content size), a skippable frame above 32 MiB.  With checksums on, a wrong checksum of a partition whose last byte
+ *          the window holds is still reported first.
+ * Malformed  S3S_E_BAD_FRAME, sticky, from the feed that meets it: a reserved block type or header bit, a block or frame that
+ *          runs past its partition's end, a partition that ends with a frame open, a Frame_Content_Size the decoded bytes do
+ *          not match, every failure of the block decoder, and an offset that reaches further back than
+ *          min(Window_Size, bytes of the frame produced so far).  The size pass covers every block of the window, also those
+ *          behind the capacity cut, and meets what is wrong with a block's headers, table descriptions and sequences; what
+ *          is wrong with its Huffman-coded literals (tree, streams, treeless literals without a tree) is met by the feed
+ *          that decodes the block.  NOTE: the one-shot call keeps the whole frame as history and may accept the offset
+ *          case; it is invalid by RFC 8878 (libzstd refuses it once the offset passes what its own window buffer still
+ *          holds).  For everything else the final verdict falls in the same class as the one-shot call's.
+ * State    NOT host-only: a Zstandard stream owns device memory between feeds, for the one frame that is open at the
+ *          position - the last min(Window_Size, produced) bytes of the frame's output, the three repeat offsets, what a later
+ *          block may reuse without restating it (the Huffman tree of treeless literals, the LL / OF / ML tables of
+ *          Repeat_Mode) and the bytes produced so far.  It is allocated (record + Window_Size bytes, sized by the frame, not
+ *          by window_log_max) when a frame first stays open across a feed, freed when the frame ends and in any case by
+ *          s3s_dstream_close, also in the middle of a range.  It is not part of the context's workspace: other calls on the
+ *          context may run between two feeds.  An allocation failure is S3S_E_NOMEM with nothing consumed; the stream stays
+ *          usable.  During a feed the workspace additionally holds the open frame's history plus what it decodes in the feed.
+ * Result   the concatenation of all dst outputs is what s3s_decompress_range_device writes for the same range, whatever
+ *          S3S_OPT_ZSTD_DECODE_VARIANT and S3S_OPT_ZSTD_DECODE_STAGED are set to.
+ * Not here frames with a content checksum, Zstandard under IO encryption, a batched feed. */
 typedef struct s3s_dstream s3s_dstream;
 typedef struct s3s_dstream_result {
   int64_t consumed;      /* bytes of this window taken; the next window starts there */
@@ -529,6 +573,12 @@ int s3s_dstream_open(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* 
                      int32_t nparts, s3s_dstream** out);
 int s3s_dstream_open_encrypted(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums,
                                int32_t nparts, s3s_dstream** out);
+int s3s_dstream_open_zstd(s3s_ctx* ctx, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums, int32_t nparts,
+                          int32_t window_log_max, s3s_dstream** out);
+/* Debug accessor (additive, detected by the symbol): the device bytes a stream holds between feeds as it allocated them - 0 for
+ * every stream but a Zstandard one with a frame open, then the state record (rounded to 256) plus that frame's Window_Size.
+ * With s == NULL: the sum over all streams of the process, which a close in the middle of a range must bring back down. */
+int64_t s3s_dstream_held_bytes(const s3s_dstream* s);
 int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_len, uint8_t* d_dst, int64_t dst_capacity,
                             s3s_dstream_result* r);
 int s3s_dstream_feed(s3s_dstream* s, const uint8_t* comp, int64_t comp_len, uint8_t* dst, int64_t dst_capacity, /* host buffers */

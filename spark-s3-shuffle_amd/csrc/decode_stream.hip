@@ -17,12 +17,20 @@
 // discovery: discovery, the emit kernels, the cut and the decoders read it with plain offsets and do not know of the layer.
 // The host maps a plain offset back by adding 16 for every IV passed.  No wait is added: the IVs that start in the window
 // come back with the first wait, and the one of the partition a feed leaves open stays in the stream (host memory).
+//
+// Zstandard (s3s_dstream_open_zstd) is the one codec whose stream is not host-only: the units are frame headers,
+// blocks and skippable frames, a block's decoded size is known only after a size pass (one more wait per feed), and the frame
+// that is open at the position keeps a state record and its last min(Window_Size, produced) bytes in device memory of the
+// stream's own.  The kernels are zstd_decode_stream.hip; the frame resumed by a feed decodes behind its saved history in a
+// staging area of the workspace and is copied to dst, frames that start in the feed decode straight into dst.
 #include <algorithm>
+#include <atomic>
 #include <new>
 
 #define S3S_AES_DEVICE
 #include "aes_ctr_core.h"
 #include "s3s_ctx.h"
+#include "zstd_decode_stream.h"
 
 using namespace s3s;
 
@@ -42,9 +50,37 @@ struct s3s_dstream {
   uint64_t epoch = 0;         // the context's key setting the stream is bound to (s3s_ctx::enc_epoch)
   std::vector<int64_t> poff;  // plain offsets of the partitions: a stored partition of 16 bytes or more loses its IV, a shorter one is empty
   uint8_t iv[16] = {};
+  // s3s_dstream_open_zstd: the one frame that is open at the position.  zmem = [ZStreamState | the last zhist_len bytes of the
+  // frame's output], device memory of the stream's own (not the context's workspace: other calls run between two feeds),
+  // allocated when a frame first stays open across a feed, sized by that frame's Window_Size, freed when the frame ends
+  int wlog = 0;               // window_log_max (0: not a Zstandard stream)
+  bool zopen = false;
+  void* zmem = nullptr;
+  int64_t zwindow = 0, zproduced = 0, zhist_len = 0;
+  int64_t zheld = 0;          // bytes of zmem as allocated
 };
 
 namespace {
+
+constexpr size_t kZStateBytes = (sizeof(s3s_zstd::ZStreamState) + 255) & ~size_t(255);  // the history bytes start behind the record
+
+// device bytes that Zstandard streams hold between feeds: this stream's (zheld) and the process's (s3s_dstream_held_bytes)
+std::atomic<int64_t> g_zheld{0};
+
+void zfree(s3s_dstream* s) {
+  if (s->zmem) (void)hipFree(s->zmem);
+  g_zheld -= s->zheld;
+  s->zheld = 0;
+  s->zmem = nullptr;
+  s->zopen = false;
+  s->zwindow = s->zproduced = s->zhist_len = 0;
+}
+struct ZNew {  // device memory of a frame that may stay open: the stream's once the feed has succeeded, freed otherwise
+  void* p = nullptr;
+  ~ZNew() {
+    if (p) (void)hipFree(p);
+  }
+};
 
 inline int64_t fresh(int algo) { return algo == S3S_CHECKSUM_ADLER32 ? 1 : 0; }  // getValue() of a new Adler32 / CRC32 / CRC32C
 
@@ -58,6 +94,7 @@ inline int64_t min_unit(const s3s_dstream* s) {
     case S3S_CODEC_LZ4: return kLz4FrameHeader;
     case S3S_CODEC_SNAPPY: return s->pos == part_start + (s->enc ? s3s_aes::kBlock : 0) ? kSnappyStreamHeader : 4;
     case S3S_CODEC_LZF: return 5;
+    case S3S_CODEC_ZSTD: return s->zopen ? 3 : 6;  // a block header; a frame header's first step
     default: return 1;
   }
 }
@@ -93,7 +130,7 @@ int64_t none_cut_encrypted(const s3s_dstream* s, int64_t len, int64_t cap) {
 }
 
 int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums, int32_t nparts,
-                s3s_dstream** out, bool encrypted) {
+                s3s_dstream** out, bool encrypted, int zstd_wlog = 0) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   if (!out) return fail(ctx, S3S_E_INVALID, "null/invalid argument");
@@ -110,8 +147,8 @@ int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_
   if (checksum_algo != S3S_CHECKSUM_NONE && nparts > 0 && !ref_checksums)
     return fail(ctx, S3S_E_INVALID, "ref_checksums is null but a checksum algorithm is selected");
   if (encrypted && !enc_on(ctx)) return fail(ctx, S3S_E_INVALID, "s3s_dstream_open_encrypted on a context without IO encryption");
-  if (codec == S3S_CODEC_ZSTD)  // a frame is a whole partition with history across its blocks: no unit to stop at
-    return fail(ctx, S3S_E_UNSUPPORTED, "Zstandard ranges cannot be streamed (use s3s_decompress_range*)");
+  if (codec == S3S_CODEC_ZSTD && !zstd_wlog)  // the units and the device state of a Zstandard stream are the opt-in of s3s_dstream_open_zstd
+    return fail(ctx, S3S_E_UNSUPPORTED, "Zstandard ranges are streamed by s3s_dstream_open_zstd (or use s3s_decompress_range*)");
   if (!encrypted && enc_on(ctx))  // the caller has to know the IV unit: s3s_dstream_open_encrypted is the opt-in
     return fail(ctx, S3S_E_UNSUPPORTED, "ranges under IO encryption are streamed by s3s_dstream_open_encrypted");
   s3s_dstream* s = new (std::nothrow) s3s_dstream();
@@ -123,6 +160,7 @@ int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, const int64_t* part_
   s->off.assign(part_offsets, part_offsets + nparts + 1);
   if (checksum_algo != S3S_CHECKSUM_NONE && nparts > 0) s->ref.assign(ref_checksums, ref_checksums + nparts);
   s->carry = fresh(checksum_algo);
+  s->wlog = zstd_wlog;
   if (encrypted) {
     s->enc = true;
     s->epoch = ctx->enc_epoch;
@@ -150,12 +188,26 @@ int s3s_dstream_open_encrypted(s3s_ctx* ctx, int codec, int checksum_algo, const
   return open_stream(ctx, codec, checksum_algo, part_offsets, ref_checksums, nparts, out, true);
 }
 
+int s3s_dstream_open_zstd(s3s_ctx* ctx, int checksum_algo, const int64_t* part_offsets, const int64_t* ref_checksums, int32_t nparts,
+                          int32_t window_log_max, s3s_dstream** out) {
+  if (!ctx) return S3S_E_INVALID;
+  if (out) *out = nullptr;
+  if (window_log_max < 10 || window_log_max > 27) return fail(ctx, S3S_E_INVALID, "window_log_max %d is outside 10 .. 27", window_log_max);
+  return open_stream(ctx, S3S_CODEC_ZSTD, checksum_algo, part_offsets, ref_checksums, nparts, out, false, window_log_max);
+}
+
+int64_t s3s_dstream_held_bytes(const s3s_dstream* s) { return s ? s->zheld : g_zheld.load(); }
+
 int64_t s3s_dstream_position(const s3s_dstream* s) { return s ? s->pos : (int64_t)S3S_E_INVALID; }
 
 int s3s_dstream_close(s3s_dstream* s) {
   if (!s) return S3S_E_INVALID;
   const int rc = s->err != S3S_OK ? s->err : at_end(s) ? S3S_OK : S3S_E_BAD_FRAME;
   wipe(s->iv, sizeof s->iv);
+  if (s->zmem) {  // (a close in the middle of a range: the open frame's state goes with the stream)
+    (void)hipSetDevice(s->ctx->device);
+    zfree(s);
+  }
   delete s;
   return rc;
 }
@@ -215,7 +267,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   const size_t o_off2 = al(8 * n1), o_seg = al(o_off2 + 16), o_seg2 = al(o_seg + 4 * n1), o_seed = al(o_seg2 + 8),
                o_sums = al(o_seed + 8 * n1), o_misc = al(o_sums + 8 * n1),
                // encrypted: [plain piece offsets n + 1][first cipher byte of every piece n + 1][the IVs that start in the window n + 1]
-               o_q = al(o_misc + 64), o_c = al(o_q + 8 * n1), o_iv = al(o_c + 8 * n1), stage_total = enc ? o_iv + 16 * n1 : o_misc + 64;
+               o_q = al(o_misc + 128), o_c = al(o_q + 8 * n1), o_iv = al(o_c + 8 * n1), stage_total = enc ? o_iv + 16 * n1 : o_misc + 128;
   int rc;
   if ((rc = ensure_stage(ctx, stage_total))) return rc;
   uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
@@ -225,7 +277,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   int32_t* h_seg2 = reinterpret_cast<int32_t*>(hs + o_seg2);
   int64_t* h_seed = reinterpret_cast<int64_t*>(hs + o_seed);
   int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);  // [n] = the second launch's sum
-  int64_t* h_misc = reinterpret_cast<int64_t*>(hs + o_misc);  // [0] n_frames, [1] status, [2..5] stop, need / k, consumed, out_len, need
+  int64_t* h_misc = reinterpret_cast<int64_t*>(hs + o_misc);  // [0] n_frames, [1] status, [2..5] stop, need / k, consumed, out_len, need; Zstandard: [6..9] open, frame unit, window, out start, [10] resumed bytes
   int64_t* h_q = reinterpret_cast<int64_t*>(hs + o_q);
   int64_t* h_c = reinterpret_cast<int64_t*>(hs + o_c);
   const uint8_t* h_iv = hs + o_iv;
@@ -292,11 +344,11 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     const int64_t plain_len = s->poff[(size_t)(s->cur + m)] - s->poff[(size_t)(s->cur + m) - 1];  // of partition cur + m - 1
     plast_pend = h_q[m - 1] + plain_len - (m == 1 ? pfront : 0);  // (m == 1: it is the open partition, pfront of it lie in front)
   }
-  // device: B_OFFSETS [piece offsets n + 1][2], B_REF_SUMS [seeds n + 1], B_SUMS [n + 1], B_STATUS [status][pad][result 4 x int64]
+  // device: B_OFFSETS [piece offsets n + 1][2], B_REF_SUMS [seeds n + 1], B_SUMS [n + 1], B_STATUS [status][pad][result 9 x int64]
   if ((rc = ensure(ctx, B_OFFSETS, 8 * (n1 + 2)))) return rc;
   if ((rc = ensure(ctx, B_REF_SUMS, 8 * n1))) return rc;
   if ((rc = ensure(ctx, B_SUMS, 8 * n1))) return rc;
-  if ((rc = ensure(ctx, B_STATUS, 64))) return rc;
+  if ((rc = ensure(ctx, B_STATUS, 128))) return rc;
   int64_t* d_off = dev<int64_t>(ctx, B_OFFSETS);
   const uint8_t* P = d_comp;      // the plain bytes of the window
   const int64_t* d_poff = d_off;  // ... and their pieces
@@ -309,7 +361,7 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   }
   int32_t* d_status = dev<int32_t>(ctx, B_STATUS);
   int64_t* d_result = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_STATUS) + 16);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, 64, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, 128, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_off, h_off, 8 * n1, hipMemcpyHostToDevice, ctx->stream));
   if (enc && m > 0 && h_off[m] > 0) {  // the decrypt pass, in front of discovery; the IVs it gathers arrive with the first wait
     uint8_t* d_iv = dev<uint8_t>(ctx, B_CRYPT_OFF) + 8 * n1;
@@ -344,14 +396,94 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
   auto refused = [&](int32_t st, const char* what) -> int {
     if (st != S3S_E_UNSUPPORTED) return corrupt(what);
     const int32_t bad = wrong_sum();
-    return bad >= 0 ? stick(s, r, S3S_E_CHECKSUM, bad, "") : fail(ctx, S3S_E_UNSUPPORTED, "codec block larger than the decoder takes");
+    if (bad >= 0) return stick(s, r, S3S_E_CHECKSUM, bad, "");
+    if (codec == S3S_CODEC_ZSTD)
+      return fail(ctx, S3S_E_UNSUPPORTED, "Zstandard frame outside the streaming contract (content checksum, dictionary id, window above "
+                                          "1 << %d, or a skippable frame above 32 MiB)", s->wlog);
+    return fail(ctx, S3S_E_UNSUPPORTED, "codec block larger than the decoder takes");
   };
 
   // ---- discovery: the whole units of the window, then the cut at dst_capacity -----------------------------------------------
   // (consumed and need_comp are plain offsets here; they are mapped back behind the cut)
   int64_t n_frames = 0, k = 0, consumed = PL, out_len = PL, need_comp = 0;
+  int64_t z_open_after = 0, z_fu = -1, z_window = 0, z_start = 0;  // Zstandard: the frame open behind the last unit taken
+  int64_t* d_zbase = nullptr;
+  ZStreamRun zrun = {};
   if (codec == S3S_CODEC_NONE || PL == 0) {  // (no plain byte: the window holds IVs, whole or cut, and nothing else)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  } else if (codec == S3S_CODEC_ZSTD) {
+    // the unit walk (counts, scan, units), the size pass over every block of the window - a compressed block's decoded size is
+    // not in its header - the scan of the sizes and the cut: as for the other codecs, with one pass more
+    const size_t cnt_bytes = al(sizeof(uint32_t) * n1);
+    if ((rc = ensure(ctx, B_PART_NFRAMES, cnt_bytes + sizeof(int64_t) * (n1 + 1)))) return rc;
+    uint32_t* d_cnt = dev<uint32_t>(ctx, B_PART_NFRAMES);
+    d_zbase = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_PART_NFRAMES) + cnt_bytes);
+    const int64_t wmax = (int64_t)1 << s->wlog;
+    launch_zstd_walk(P, d_poff, pn, s->zopen ? 1 : 0, plast_pend, wmax, false, nullptr, d_cnt, nullptr, nullptr, d_status, d_result, ctx->stream);
+    launch_scan_u32(d_cnt, pn, d_zbase, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&h_misc[0], d_zbase + pn, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&h_misc[1], d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&h_misc[2], d_result, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*reinterpret_cast<int32_t*>(&h_misc[1]) != 0) return refused(*reinterpret_cast<int32_t*>(&h_misc[1]), "frame or block header");
+    n_frames = h_misc[0];
+    const int64_t stop = h_misc[2];
+    need_comp = h_misc[3];
+    if (stop < 0 || stop > PL || (stop < PL && need_comp <= PL - stop)) return fail(ctx, S3S_E_HIP, "unit discovery returned an impossible stop offset");
+    if (n_frames > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "too many units in one feed");
+    k = 0;
+    consumed = stop;
+    out_len = 0;
+    z_open_after = s->zopen ? 1 : 0;
+    if (n_frames > 0) {
+      if ((rc = ensure(ctx, B_FRAMES, sizeof(s3s_zstd::ZUnit) * (size_t)(n_frames + 1)))) return rc;
+      if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_frames + 1)))) return rc;
+      if ((rc = ensure(ctx, B_FRAME_OUT, sizeof(int64_t) * (size_t)(n_frames + 1)))) return rc;
+      launch_zstd_walk(P, d_poff, pn, s->zopen ? 1 : 0, plast_pend, wmax, true, d_zbase, nullptr, ctx->buf[B_FRAMES].p,
+                       dev<uint32_t>(ctx, B_ITEM_SIZE), d_status, d_result, ctx->stream);
+      zrun.comp = P;
+      zrun.units = dev<s3s_zstd::ZUnit>(ctx, B_FRAMES);
+      zrun.dsize = dev<uint32_t>(ctx, B_ITEM_SIZE);
+      zrun.unit_out = dev<int64_t>(ctx, B_FRAME_OUT);
+      zrun.unit_base = d_zbase;
+      zrun.k = n_frames;
+      zrun.execute = 0;
+      zrun.resumed = s->zopen ? 1 : 0;
+      zrun.st_in = static_cast<const s3s_zstd::ZStreamState*>(s->zmem);
+      zrun.st_out = nullptr;
+      zrun.dst = d_dst;
+      zrun.staging = nullptr;
+      zrun.hist_len = s->zhist_len;
+      zrun.lit = nullptr;
+      zrun.lit_stride = 0;
+      zrun.status = d_status;
+      zrun.result = d_result + 8;
+      launch_zstd_stream(zrun, pn, ctx->stream);  // the size pass: no stores but the sizes, the saved state is only read
+      launch_scan_u32(dev<uint32_t>(ctx, B_ITEM_SIZE), n_frames, dev<int64_t>(ctx, B_FRAME_OUT), ctx->stream);
+      launch_zstd_units_cut(P, ctx->buf[B_FRAMES].p, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_FRAME_OUT), n_frames, dst_capacity,
+                            stop, s->zopen ? 1 : 0, d_result, ctx->stream);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(&h_misc[1], d_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(&h_misc[2], d_result, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      if (*reinterpret_cast<int32_t*>(&h_misc[1]) != 0) return refused(*reinterpret_cast<int32_t*>(&h_misc[1]), "block");
+      k = h_misc[2];
+      consumed = h_misc[3];
+      out_len = h_misc[4];
+      if (k < 0 || k > n_frames || consumed < 0 || consumed > stop || out_len < 0 || out_len > dst_capacity)
+        return fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible unit index");
+      if (consumed == 0) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
+        r->need_dst = h_misc[5];
+        return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld decoded bytes of the next block", (long long)dst_capacity, (long long)h_misc[5]);
+      }
+      z_open_after = h_misc[6];
+      z_fu = h_misc[7];
+      z_window = h_misc[8];
+      z_start = h_misc[9];
+      if (z_open_after && z_fu >= 0 && (z_window < 0 || z_window > wmax || z_start < 0 || z_start > out_len))
+        return fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible open frame");
+    }
   } else {
     const int cf = codec == S3S_CODEC_LZF ? kChunkLzf : kChunkSnappy;
     const int32_t n_tiles = codec == S3S_CODEC_LZ4 ? lz4_tile_count(PL) : 0;
@@ -455,7 +587,40 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     HIP_TRY(ctx, hipMemcpyAsync(d_dst, P, (size_t)out_len, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   } else if (k > 0 || second) {
-    if (k > 0) {
+    ZNew z_new;
+    if (k > 0 && codec == S3S_CODEC_ZSTD) {
+      // the frame that was open decodes behind its saved history in a staging area, so that every offset it may use is there;
+      // a frame that starts in this feed and stays open gets its memory now: a failure consumes nothing
+      if (z_open_after && z_fu >= 0) {
+        const size_t bytes = kZStateBytes + (size_t)(z_window > 0 ? z_window : 1);
+        if (hipMalloc(&z_new.p, bytes) != hipSuccess) {
+          (void)hipGetLastError();
+          z_new.p = nullptr;
+          r->consumed = r->out_len = 0;
+          return fail(ctx, S3S_E_NOMEM, "hipMalloc(%zu) for the open frame's history failed", bytes);
+        }
+      }
+      int64_t max_piece = 0;
+      for (int32_t i = 0; i < pn; i++) max_piece = std::max(max_piece, h_off[i + 1] - h_off[i]);
+      const int64_t by_size = 8 * max_piece + 256;
+      const int64_t lit_stride = ((std::min<int64_t>(by_size, s3s_zstd::kMaxBlock) + 64) + 15) & ~int64_t(15);
+      if ((rc = ensure(ctx, B_ZBLOCK_LIT, (size_t)lit_stride * (size_t)pn + 64))) return rc;
+      if (s->zopen) {
+        if ((rc = ensure(ctx, B_ZSCRATCH, (size_t)(s->zhist_len + out_len) + 256))) return rc;
+        if (s->zhist_len > 0)
+          HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_ZSCRATCH].p, static_cast<uint8_t*>(s->zmem) + kZStateBytes, (size_t)s->zhist_len,
+                                      hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      zrun.k = k;
+      zrun.execute = 1;
+      zrun.st_out = !z_open_after ? nullptr : static_cast<s3s_zstd::ZStreamState*>(z_fu >= 0 ? z_new.p : s->zmem);
+      zrun.staging = s->zopen ? dev<uint8_t>(ctx, B_ZSCRATCH) : nullptr;
+      zrun.lit = dev<uint8_t>(ctx, B_ZBLOCK_LIT);
+      zrun.lit_stride = lit_stride;
+      launch_zstd_stream(zrun, pn, ctx->stream);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(&h_misc[10], d_result + 8, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    } else if (k > 0) {
       if (codec == S3S_CODEC_LZ4)
         launch_lz4_decompress(P, dev<Frame>(ctx, B_FRAMES), (int32_t)k, dev<int64_t>(ctx, B_FRAME_OUT), d_dst, d_status,
                               ctx->lz4_decode_variant, ctx->stream);
@@ -487,6 +652,41 @@ int s3s_dstream_feed_device(s3s_dstream* s, const uint8_t* d_comp, int64_t comp_
     if (st == S3S_E_UNSUPPORTED) return fail(ctx, S3S_E_UNSUPPORTED, "codec block larger than the decoder takes");
     if (st != 0) return corrupt("frame payload");  // (the capacity cut may have left a partition's end, which the window holds, unconsumed)
     if (second) carry = h_sums[n];
+    if (k > 0 && codec == S3S_CODEC_ZSTD) {  // the resumed frame's bytes to dst, the open frame's last bytes to the stream
+      const int64_t resumed_out = s->zopen ? h_misc[10] : 0;
+      if (resumed_out < 0 || resumed_out > out_len || (z_open_after && z_fu < 0 && resumed_out != out_len))
+        return fail(ctx, S3S_E_HIP, "the resumed frame reported an impossible size");
+      const uint8_t* staging = dev<uint8_t>(ctx, B_ZSCRATCH);
+      if (resumed_out > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(d_dst, staging + s->zhist_len, (size_t)resumed_out, hipMemcpyDeviceToDevice, ctx->stream));
+      if (!z_open_after) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        zfree(s);
+      } else if (z_fu < 0) {  // still the same frame
+        const int64_t produced = s->zproduced + out_len, nh = std::min(s->zwindow, produced), end = s->zhist_len + out_len;
+        if (nh > 0)
+          HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(s->zmem) + kZStateBytes, staging + (end - nh), (size_t)nh, hipMemcpyDeviceToDevice,
+                                      ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        s->zproduced = produced;
+        s->zhist_len = nh;
+      } else {  // a frame that started in this feed
+        const int64_t produced = out_len - z_start, nh = std::min(z_window, produced);
+        if (nh > 0)
+          HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(z_new.p) + kZStateBytes, d_dst + (out_len - nh), (size_t)nh, hipMemcpyDeviceToDevice,
+                                      ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        zfree(s);
+        s->zmem = z_new.p;
+        z_new.p = nullptr;
+        s->zheld = (int64_t)(kZStateBytes + (size_t)(z_window > 0 ? z_window : 1));
+        g_zheld += s->zheld;
+        s->zopen = true;
+        s->zwindow = z_window;
+        s->zproduced = produced;
+        s->zhist_len = nh;
+      }
+    }
   }
 
   if (enc && q < np && new_pos > s->off[(size_t)q] && !(q == s->cur && front > 0))  // the open partition's IV: it started in this window

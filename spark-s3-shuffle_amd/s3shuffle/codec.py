@@ -170,6 +170,11 @@ def load_library() -> ctypes.CDLL:
         lib.s3s_dstream_close.argtypes = [vp]
     if hasattr(lib, "s3s_dstream_open_encrypted"):  # streams under IO encryption (additive, detected by the symbol)
         lib.s3s_dstream_open_encrypted.argtypes = lib.s3s_dstream_open.argtypes
+    if hasattr(lib, "s3s_dstream_open_zstd"):  # resumable Zstandard streams (additive, detected by the symbol)
+        lib.s3s_dstream_open_zstd.argtypes = [vp, ctypes.c_int, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]
+    if hasattr(lib, "s3s_dstream_held_bytes"):  # debug accessor: device bytes a stream (or, with NULL, all streams) holds between feeds
+        lib.s3s_dstream_held_bytes.restype = ctypes.c_int64
+        lib.s3s_dstream_held_bytes.argtypes = [vp]
     _LIB = lib
     return lib
 
@@ -407,10 +412,13 @@ class Codec:
         return out[:n]
 
     # ---- reduce side ---------------------------------------------------------------------------
-    def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False) -> "DecodeStream":
+    def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False,
+                      window_log_max: Optional[int] = None) -> "DecodeStream":
         """A fetched range decoded window by window in bounded memory (s3s_dstream_*); `encrypted`: a range stored under IO
-        encryption, through s3s_dstream_open_encrypted (offsets, windows and positions count the stored bytes, IVs included)."""
-        return DecodeStream(self, codec, checksum, part_offsets, ref_checksums, encrypted=encrypted)
+        encryption, through s3s_dstream_open_encrypted (offsets, windows and positions count the stored bytes, IVs included);
+        `window_log_max` (10 .. 27, with ZSTD): a resumable Zstandard stream through s3s_dstream_open_zstd, which keeps at most
+        1 << window_log_max bytes of history on the device for its open frame."""
+        return DecodeStream(self, codec, checksum, part_offsets, ref_checksums, encrypted=encrypted, window_log_max=window_log_max)
 
     def decompressed_size(self, codec: int, comp: np.ndarray) -> int:
         comp = np.ascontiguousarray(comp, dtype=np.uint8)
@@ -502,9 +510,13 @@ class DecodeStream:
     `close()` raises E_BAD_FRAME when the range was not read to its end.  Also a context manager (which closes quietly after
     an exception, loudly otherwise).
     `encrypted=True` opens the stream with s3s_dstream_open_encrypted (the context's IO encryption must be on): a partition's
-    16-byte IV is a unit of its own that decodes to nothing, and the stream is bound to the key setting it was opened under."""
+    16-byte IV is a unit of its own that decodes to nothing, and the stream is bound to the key setting it was opened under.
+    `window_log_max=N` with ZSTD opens the stream with s3s_dstream_open_zstd: the units are frame headers, blocks and skippable
+    frames, and the stream owns device memory (the open frame's history, at most 1 << N bytes) until the frame ends or `close()`.
+    ZSTD without it is refused at open, as before."""
 
-    def __init__(self, codec_ctx: Codec, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False):
+    def __init__(self, codec_ctx: Codec, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False,
+                 window_log_max: Optional[int] = None):
         self._ctx = codec_ctx
         self._lib = codec_ctx._lib
         offs = _i64(part_offsets)
@@ -514,14 +526,27 @@ class DecodeStream:
         self.last_result = None
         if encrypted and not hasattr(self._lib, "s3s_dstream_open_encrypted"):
             raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_dstream_open_encrypted")
-        fn = self._lib.s3s_dstream_open_encrypted if encrypted else self._lib.s3s_dstream_open
-        rc = fn(codec_ctx._h, codec, checksum, _p64(offs), _p64(refs) if refs is not None else None, len(offs) - 1, ctypes.byref(h))
+        if window_log_max is not None:
+            if codec != CODEC_ZSTD or encrypted:
+                raise ValueError("window_log_max goes with ZSTD and without `encrypted`")
+            if not hasattr(self._lib, "s3s_dstream_open_zstd"):
+                raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_dstream_open_zstd")
+            rc = self._lib.s3s_dstream_open_zstd(codec_ctx._h, checksum, _p64(offs), _p64(refs) if refs is not None else None,
+                                                 len(offs) - 1, int(window_log_max), ctypes.byref(h))
+        else:
+            fn = self._lib.s3s_dstream_open_encrypted if encrypted else self._lib.s3s_dstream_open
+            rc = fn(codec_ctx._h, codec, checksum, _p64(offs), _p64(refs) if refs is not None else None, len(offs) - 1, ctypes.byref(h))
         codec_ctx._check(rc)
         self._s = h.value
 
     @property
     def position(self) -> int:
         return int(self._lib.s3s_dstream_position(self._s))
+
+    @property
+    def held_device_bytes(self) -> int:
+        """Device bytes the stream holds between feeds (s3s_dstream_held_bytes): 0 unless a Zstandard frame is open."""
+        return int(self._lib.s3s_dstream_held_bytes(self._s)) if self._s else 0
 
     def _feed(self, fn, comp_ptr, comp_len, dst_ptr, dst_capacity):
         if not self._s:
