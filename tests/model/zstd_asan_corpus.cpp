@@ -4,6 +4,8 @@
 // write one byte outside either stops the run with a sanitizer report; the result is compared with the expected content or the
 // expected refusal.
 //   usage: zstd_asan_corpus <case file>     records: u32 compressed size, u32 content size, i32 expected status, the bytes, the content
+//          zstd_asan_corpus --cap <case file>   the same records with an i64 destination capacity behind the expected status
+//                                               (tests/test_zstd_mutants_model.py: a mutant's capacity is part of the case)
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -15,7 +17,8 @@ using namespace s3s_zstd;
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
+  const bool with_cap = argc > 2 && !strcmp(argv[1], "--cap");
+  FILE* f = fopen(argv[with_cap ? 2 : 1], "rb");
   if (!f) return 2;
   static Work w_size, w_dec;
   static LitPipe lp_size, lp_dec;
@@ -24,12 +27,14 @@ int main(int argc, char** argv) {
   for (;;) {
     uint32_t n = 0, usize = 0;
     int32_t want = 0;
+    int64_t given_cap = 0;
     if (fread(&n, 4, 1, f) != 1 || fread(&usize, 4, 1, f) != 1 || fread(&want, 4, 1, f) != 1) break;
+    if (with_cap && fread(&given_cap, 8, 1, f) != 1) return 2;
     std::unique_ptr<uint8_t[]> comp(new uint8_t[n ? n : 1]);
     std::unique_ptr<uint8_t[]> content(new uint8_t[usize ? usize : 1]);
     if (n && fread(comp.get(), 1, n, f) != n) return 2;
     if (usize && fread(content.get(), 1, usize, f) != usize) return 2;
-    const int64_t cap = want == 0 ? (int64_t)usize : 65536;
+    const int64_t cap = with_cap ? given_cap : want == 0 ? (int64_t)usize : 65536;
     std::unique_ptr<uint8_t[]> dst(new uint8_t[cap ? cap : 1]);
     Lanes L{0, 1};
     int64_t total = -1, total2 = -1;

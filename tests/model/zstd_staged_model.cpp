@@ -146,6 +146,8 @@ extern "C" void zg_caps(int64_t comp_bytes, int64_t* caps) {
 #ifdef ZG_MAIN
 // cases file: u32 count, then per case i64 size | i64 content size (-1: the partition is invalid) | i64 capacity | i32 block path in
 // front | i32 expected staged frames | i32 expected dependent frames | i32 expected staged blocks | source bytes | content bytes
+// Verdict only (tests/test_zstd_mutants_model.py): the three counts are -1 and are not compared - the verdict, the bytes and the
+// serial decoder's agreement are.
 template <typename T>
 static bool rd(FILE* f, T* v, size_t n = 1) { return fread(v, sizeof(T), n, f) == n; }
 #define CHECK(c)                                                             \
@@ -182,9 +184,11 @@ int main(int argc, char** argv) {
     } else {
       CHECK(rc != ZS_OK);
     }
-    CHECK(info[0] == want_frames);
-    CHECK(info[2] == want_dep);
-    CHECK(info[3] == want_blocks);
+    if (!(want_frames == -1 && want_dep == -1 && want_blocks == -1)) {
+      CHECK(info[0] == want_frames);
+      CHECK(info[2] == want_dep);
+      CHECK(info[3] == want_blocks);
+    }
     free(src);
     free(content);
     free(dst);

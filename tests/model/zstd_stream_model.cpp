@@ -8,6 +8,8 @@
 //   zstd_stream_model decode <file>   cases: i64 n, i64 content size (-1: none; with an expected code != 0: what the output must be a prefix of), i32 expected code, i32 wlog, i64 cap
 //                                     (0: unlimited), i32 mode (0: the cuts given, 1: a feed per unit, 2: one byte short of and one
 //                                     byte past every unit boundary), i32 ncuts, ncuts x i64 window ends, the bytes, the content
+//   zstd_stream_model report <file>   the same cases, nothing expected of them (the expected code and the content are ignored):
+//                                     one line per case - the code the stream ended with, the bytes it handed out, their CRC32
 //   zstd_stream_model units <file>    records: i64 L, i64 pend, i32 open, i32 wlog, L bytes  ->  one line per record:
 //                                     n stop need, then off:kind:payload per unit
 #include <algorithm>
@@ -197,6 +199,19 @@ int run_case(const uint8_t* part, int64_t n, int wlog, int64_t cap, int mode, st
   return 0;
 }
 
+uint32_t crc32_of(const uint8_t* p, size_t n) {  // (zlib's: the caller compares it with zlib.crc32 of the bytes it expects)
+  static uint32_t table[256];
+  if (!table[1])
+    for (uint32_t i = 0; i < 256; i++) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+      table[i] = c;
+    }
+  uint32_t c = 0xFFFFFFFFu;
+  for (size_t i = 0; i < n; i++) c = table[(c ^ p[i]) & 255] ^ (c >> 8);
+  return ~c;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -224,6 +239,7 @@ int main(int argc, char** argv) {
     fclose(f);
     return 0;
   }
+  const bool report = !strcmp(argv[1], "report");
   long n_cases = 0, n_wrong = 0;
   for (;;) {
     int64_t n, usize, cap;
@@ -239,6 +255,11 @@ int main(int argc, char** argv) {
     if (usize > 0 && fread(content.get(), 1, (size_t)usize, f) != (size_t)usize) return 2;
     std::vector<uint8_t> out;
     const int rc = run_case(part.get(), n, wlog, cap, mode, cuts, out);
+    if (report) {  // nothing is expected: what the stream answered, for the caller to judge
+      printf("%d %zu %u\n", rc, out.size(), crc32_of(out.data(), out.size()));
+      n_cases++;
+      continue;
+    }
     bool ok = rc == want;
     if (ok && want == 0) ok = (int64_t)out.size() == usize && (usize == 0 || memcmp(out.data(), content.get(), (size_t)usize) == 0);
     // refused or corrupt with a content given: what was handed out before the verdict is a prefix of it
@@ -248,6 +269,7 @@ int main(int argc, char** argv) {
     n_cases++;
   }
   fclose(f);
+  if (report) return 0;
   printf("zstd_stream_model: %ld cases, %ld wrong\n", n_cases, n_wrong);
   return n_wrong ? 1 : 0;
 }

@@ -7,7 +7,18 @@ of them damaged (bit flips, random bytes, truncations, splices) - and decodes th
 s3s_decompress_ranges_batch_device call, so that hundreds of workgroups with damaged streams run the literal wavefront, the lean
 sequence loop and the compiled loop side by side on the real machine.  Per partition the verdict must be libzstd's: refused
 (bad frame / capacity), or the same bytes (a few per cent differ in the two documented directions: the product refuses a sequence
-stream that reads below its first bit; libzstd refuses offsets beyond its window, the product's history is the whole frame).  A hang would show as the call not returning (the polls are bounded: kPipeSpins)."""
+stream that reads below its first bit; libzstd refuses offsets beyond its window, the product's history is the whole frame).  A hang would show as the call not returning (the polls are bounded: kPipeSpins).
+
+Those inputs are libzstd level-1 frames with history, which stay on the serial decoder at the default options.  For a campaign
+on the newer paths:
+
+    python tests/tools/gpu_zstd_fuzz.py --family writer --variant 1 --parts 250        # one workgroup per block (key 13)
+    python tests/tools/gpu_zstd_fuzz.py --family flushed4k --staged 1 --parts 250      # the staged path (key 15)
+
+--family takes each round's partitions from tests/zstd_mutants.py (seed 1000 * --seed + round) instead; --variant / --staged set
+S3S_OPT_ZSTD_DECODE_VARIANT / S3S_OPT_ZSTD_DECODE_STAGED and print the blocks keys 14 / 16 counted.  (In a call of 4 x CUs
+partitions or more the block path only takes frames of 10 blocks and more: keep --parts below that.)  tests/test_gpu_zstd_mutants.py
+is the short, exact form of this: it compares with the host models instead of libzstd."""
 import argparse
 import os
 import sys
@@ -29,6 +40,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--parts", type=int, default=300)
     ap.add_argument("--host-model", action="store_true", help="decode with the host build of the same core instead (no GPU): the verdict counts must be the GPU run's")
+    ap.add_argument("--variant", type=int, choices=[0, 1], default=None, help="S3S_OPT_ZSTD_DECODE_VARIANT (key 13); default: the library's")
+    ap.add_argument("--staged", type=int, choices=[0, 1], default=None, help="S3S_OPT_ZSTD_DECODE_STAGED (key 15); default: the library's")
+    ap.add_argument("--family", choices=["writer", "flushed4k"], default=None, help="mutants of tests/zstd_mutants.py instead of the inputs above")
     a = ap.parse_args()
     from oracle import zstd_ref as z
     from s3shuffle import datagen
@@ -52,12 +66,20 @@ def main():
     if not a.host_model:
         codec = s3shuffle.Codec(0)
         dev = Dev()
+        if a.variant is not None:
+            codec.set_option(13, a.variant)
+        if a.staged is not None:
+            codec.set_option(15, a.staged)
     n_ok = n_ref = n_strict = n_lenient = 0
     strict_by = {}
     t0 = time.time()
     for rnd in range(a.rounds):
         parts = []
-        for k in range(a.parts):
+        if a.family:
+            import zstd_mutants
+
+            parts = [(np.frombuffer(data, np.uint8).copy(), size) for _, data, size, _ in zstd_mutants.mutants(a.family, 1000 * a.seed + rnd, a.parts)]
+        for k in range(0 if a.family else a.parts):
             src = tera if rng.integers(0, 2) else wide
             n = int(rng.choice([1000, 20_000, 140_000, 300_000, 700_000], p=[0.2, 0.3, 0.2, 0.2, 0.1]))
             at = int(rng.integers(0, src.size - n))
@@ -118,6 +140,8 @@ def main():
                 n_ref += 1
         if dev:
             dev.free()  # (every buffer of the round)
+            if a.variant is not None or a.staged is not None:
+                print(f"round {rnd}: blocks completed on the block path {codec.get_option(14)}, on the staged path {codec.get_option(16)}")
         print(f"round {rnd}: {n_ok} decoded like libzstd, {n_ref} refused ({n_strict} of them accepted by libzstd), {n_lenient} decoded where libzstd refuses, {time.time() - t0:.0f} s", flush=True)
     assert n_strict <= 0.03 * (n_ok + n_ref) + 2 and n_lenient <= 0.03 * (n_ok + n_ref) + 2, (n_strict, n_lenient)
     print(f"DONE seed {a.seed}: {a.rounds * a.parts} partitions, {n_ok} decoded like libzstd, {n_ref} refused, {n_strict} strict {strict_by}, {n_lenient} lenient, 0 failures")

@@ -30,8 +30,17 @@ def program():
     return exe
 
 
-def _run(mode, path):
-    return subprocess.run([program(), mode, path], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+def plain_program():
+    """The same program without the sanitizers, for the report a GPU test compares the device with (sanitizers stay on the CPU side)."""
+    exe = os.path.join(HERE, "model", "zstd_stream_model_plain")
+    if not os.path.exists(exe) or max(os.path.getmtime(p) for p in [SRC] + CORES) > os.path.getmtime(exe):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe], check=True)
+    return exe
+
+
+def _run(mode, path, sanitized=True):
+    return subprocess.run([program() if sanitized else plain_program(), mode, path], capture_output=True, text=True,
+                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
 
 
 def run_decode(cases, workdir):
@@ -47,6 +56,24 @@ def run_decode(cases, workdir):
             if content:
                 f.write(content)
     return _run("decode", path)
+
+
+def run_report(cases, workdir, sanitized=True):
+    """cases: [(partition bytes, wlog, cap, mode, cuts)] -> [(code, bytes handed out, their CRC32)]: what the stream answers,
+    nothing expected of it (the same sanitized program; a sanitizer report fails here)"""
+    path = os.path.join(workdir, "report.bin")
+    with open(path, "wb") as f:
+        for comp, wlog, cap, mode, cuts in cases:
+            comp = bytes(comp)
+            f.write(struct.pack("<qqiiqii", len(comp), -1, 0, wlog, cap, mode, len(cuts)))
+            f.write(struct.pack("<%dq" % len(cuts), *cuts))
+            f.write(comp)
+    r = _run("report", path, sanitized)
+    os.remove(path)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
+    out = [tuple(int(x) for x in line.split()) for line in r.stdout.splitlines()]
+    assert len(out) == len(cases)
+    return out
 
 
 def run_units(records, workdir):
