@@ -1,6 +1,6 @@
 """Test helpers that build codec streams WITHOUT the oracle and without the product: LZ4Block / SnappyInputStream
 framing around arbitrary block payloads, a sequence-level LZ4 / Snappy block writer for hand-made (also malformed)
-blocks, and tiny reference decoders.  Used by the decoder hardening tests.
+blocks, an element-level LZF block writer with compress-lzf's ZV chunk header, and tiny reference decoders.  Used by the decoder hardening tests.
 
 Framing follows [EXT] lz4-java LZ4BlockOutputStream / snappy-java SnappyOutputStream as restated in SURVEY.md §8
 rows a3 / a4."""
@@ -20,11 +20,12 @@ def xxh32(data: bytes, seed: int = LZ4_SEED) -> int:
     return xxhash.xxh32(data, seed=seed).intdigest()
 
 
-def lz4_frame(payload: bytes, orig: bytes, raw: bool = False, check: Optional[int] = None) -> bytes:
-    """One LZ4Block frame: magic | token | compressedLen LE | originalLen LE | check LE | payload."""
+def lz4_frame(payload: bytes, orig: bytes, raw: bool = False, check: Optional[int] = None, level: int = 5) -> bytes:
+    """One LZ4Block frame: magic | token | compressedLen LE | originalLen LE | check LE | payload.
+    level: the token's low nibble, log2(the writer's block size) - 10 (5 = 32 KiB, lz4-java's and Spark's default)."""
     if check is None:
         check = xxh32(orig) & 0x0FFFFFFF
-    token = 0x15 if raw else 0x25
+    token = (0x10 if raw else 0x20) | level
     return b"LZ4Block" + bytes([token]) + struct.pack("<iiI", len(payload), len(orig), check) + payload
 
 
@@ -227,6 +228,72 @@ def snappy_decode_py(block: bytes, max_out: int = 1 << 20) -> Optional[bytes]:
         for _ in range(ln):
             out.append(out[-off])
     return bytes(out) if len(out) == ulen else None
+
+
+# ---- LZF blocks from elements (liblzf's block format inside compress-lzf's ZV chunks) ------------------------------
+def lzf_block(elements: Sequence[tuple]) -> bytes:
+    """elements: ("lit", bytes of 1 .. 32) | ("ref", distance 1 .. 8192, length 3 .. 264).
+    ctrl < 32: ctrl + 1 literals follow; else length = (ctrl >> 5) + 2, the value 7 meaning 7 + the next byte (+ 2), and
+    distance = ((ctrl & 31) << 8 | last byte) + 1.  Lengths 3 .. 8 take the short form, 9 .. 264 the long one."""
+    out = bytearray()
+    for e in elements:
+        if e[0] == "lit":
+            assert 1 <= len(e[1]) <= 32
+            out.append(len(e[1]) - 1)
+            out += e[1]
+        else:
+            dist, ln = e[1], e[2]
+            assert 1 <= dist <= 8192 and 3 <= ln <= 264
+            d, l = dist - 1, ln - 2
+            if l < 7:
+                out.append((l << 5) | (d >> 8))
+            else:
+                out.append((7 << 5) | (d >> 8))
+                out.append(l - 7)
+            out.append(d & 0xFF)
+    return bytes(out)
+
+
+def lzf_chunk(block: bytes, ulen: int, stored: bool = False) -> bytes:
+    """compress-lzf chunk: 'Z' 'V' 1 | u16 BE block length | u16 BE decoded length | block, or, stored,
+    'Z' 'V' 0 | u16 BE length | bytes (ulen is then the length of `block`)."""
+    if stored:
+        assert ulen == len(block)
+        return b"ZV\x00" + struct.pack(">H", len(block)) + block
+    return b"ZV\x01" + struct.pack(">HH", len(block), ulen) + block
+
+
+def lzf_decode_py(block: bytes, max_out: int = 1 << 20) -> Optional[bytes]:
+    """Plain LZF block decoder (None if malformed or longer than max_out)."""
+    ip, n, out = 0, len(block), bytearray()
+    while ip < n:
+        ctrl = block[ip]
+        ip += 1
+        if ctrl < 32:
+            ln = ctrl + 1
+            if ip + ln > n:
+                return None
+            out += block[ip:ip + ln]
+            ip += ln
+        else:
+            ln = ctrl >> 5
+            if ln == 7:
+                if ip >= n:
+                    return None
+                ln += block[ip]
+                ip += 1
+            ln += 2
+            if ip >= n:
+                return None
+            dist = (((ctrl & 31) << 8) | block[ip]) + 1
+            ip += 1
+            if dist > len(out):
+                return None
+            for _ in range(ln):
+                out.append(out[-dist])
+        if len(out) > max_out:
+            return None
+    return bytes(out)
 
 
 def liblz4():

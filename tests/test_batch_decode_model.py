@@ -12,6 +12,7 @@ import pytest
 
 import corpus
 import framing
+from decoder_shapes import _chain_sequences  # noqa: F401  (the generator lives with the corpus now)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "model", "lz4_batch_decode_model.cpp")
@@ -96,42 +97,6 @@ def test_lz4_hand_made_blocks(model):
         for olen in (len(want) - 1, len(want) + 1):
             if olen > 0:
                 assert run(model, LZ4, blk, olen)[0] == -1, (i, olen)
-
-
-def _chain_sequences(rng, n_seq, max_out=30000):
-    """Random (literal length, offset, match length) lists in which matches copy from inside earlier matches, from
-    literal runs, from periodic patterns and across several of them — what the decoder's source redirection
-    (a match inside the output of one earlier match reads from that match's source) has to get right."""
-    seqs, pos, regions = [], 0, []  # regions: (start, end) of earlier match outputs
-    for _ in range(n_seq):
-        lit = int(rng.choice([0, 0, 0, 1, 2, 3, 5, 10, 14, 15, 16, 40]))
-        pos += lit
-        if pos == 0:
-            lit = 4
-            pos = 4
-        ml = int(rng.choice([4, 5, 7, 8, 15, 16, 17, 19, 29, 32, 33, 48, 59, 64, 65, 100]))
-        how = rng.integers(0, 8)
-        if how <= 2 and regions:      # wholly inside one earlier match output (the last few)
-            rs, re_ = regions[-int(rng.integers(1, min(len(regions), 6) + 1))]
-            ml = min(ml, re_ - rs)
-            src = int(rng.integers(rs, re_ - ml + 1))
-            off = pos - src
-        elif how == 3:                # short period
-            off = int(rng.choice([1, 2, 3, 4, 5, 8]))
-        elif how == 4 and regions:    # straddles the end of an earlier match output
-            rs, re_ = regions[-1]
-            off = pos - max(re_ - 2, 0)
-        elif how == 5:                # into the own literals
-            off = max(1, min(lit, pos))
-        else:
-            off = int(rng.integers(1, pos + 1))
-        off = max(1, min(off, pos, 65535))
-        seqs.append((lit, off, ml))
-        regions.append((pos, pos + ml))
-        pos += ml
-        if pos > max_out:
-            break
-    return seqs
 
 
 def test_redirected_sources(model):

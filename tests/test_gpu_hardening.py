@@ -145,12 +145,6 @@ def test_snappy_foreign_valid_and_malformed_blocks(gpu_codec):
         assert rc == -3, (i, rc)
 
 
-def _lzf_chunk(block: bytes, ulen: int) -> bytes:
-    import struct
-
-    return b"ZV\x01" + struct.pack(">HH", len(block), ulen) + block
-
-
 def test_lzf_mutated_streams_agree_with_the_oracle_and_stay_inside(gpu_codec, oracle, decode_variant):
     """round 4: LZF chunk streams (liblzf-written blocks from tests/golden/lzf_liblzf.npz and the oracle's encoder) under random
     damage - flipped bits in chunk headers and block payloads, truncations, spliced chunks: the GPU decoder gives the oracle's
@@ -162,7 +156,7 @@ def test_lzf_mutated_streams_agree_with_the_oracle_and_stay_inside(gpu_codec, or
     rng = np.random.default_rng(77)
     seeds = []
     for n in ("records", "runs", "mixed", "far"):
-        seeds.append((_lzf_chunk(g["lzf_" + n].tobytes(), g["raw_" + n].size), g["raw_" + n].size))
+        seeds.append((framing.lzf_chunk(g["lzf_" + n].tobytes(), g["raw_" + n].size), g["raw_" + n].size))
     d = corpus.chunk_corpus(7, 90_000, rng)
     s = oracle.compress_map_output(4, 0, d, [0, d.size])[0].tobytes()
     seeds.append((s, d.size))

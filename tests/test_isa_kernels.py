@@ -377,17 +377,17 @@ def test_compiled_element_parse_block_takes_the_interior_windows(oracle, fmt):
 
 def test_compiled_decoder_on_chained_sources(oracle):
     """hand-made sequence lists whose matches copy from inside earlier matches, from literal runs and from periodic
-    patterns (the generator of tests/test_batch_decode_model.py): what the decoder's source redirection, its 16-byte
+    patterns (the generator of tests/decoder_shapes.py): what the decoder's source redirection, its 16-byte
     pieces and the period splats have to get right — through the COMPILED kernel, both formats, plus TeraSort blocks"""
     import decode_kernel as dk
     import framing
-    import test_batch_decode_model as tm
+    import decoder_shapes as ds
     from s3shuffle import datagen
 
     rng = np.random.default_rng(7)
     lz, sn = [], []
     for _ in range(8):
-        seqs = tm._chain_sequences(rng, int(rng.integers(50, 400)))
+        seqs = ds._chain_sequences(rng, int(rng.integers(50, 400)))
         blk = framing.lz4_block([(rng.integers(0, 256, l).astype(np.uint8).tobytes(), o, m) for l, o, m in seqs], b"abcdefg")
         lz.append((blk, framing.lz4_decode_py(blk)))
         els = []
@@ -420,14 +420,14 @@ def test_compiled_batch_decoder_takes_blocks_above_32k(oracle):
     payload and destination of exactly their sizes; a malformed big block is S3S_E_BAD_FRAME without leaving its buffers"""
     import decode_kernel as dk
     import framing
-    import test_batch_decode_model as tm
+    import decoder_shapes as ds
     from s3shuffle import datagen
 
     rng = np.random.default_rng(47)
     big1 = datagen.terasort_map_output(70_000, 1, seed=5)[0]
     big2 = np.concatenate([datagen.tpcds_wide_map_output(100_000, 1, seed=6)[0][:100_000], corpus.chunk_corpus(7, 50_000, rng)])
     cases = [(bytes(framing.lz4_fast(big1)), big1.tobytes()), (framing.lz4_hc(big2, 9), big2.tobytes())]
-    seqs = tm._chain_sequences(rng, 6000, max_out=60_000)
+    seqs = ds._chain_sequences(rng, 6000, max_out=60_000)
     b = framing.lz4_block([(rng.integers(0, 256, l).astype(np.uint8).tobytes(), o, m) for l, o, m in seqs], b"abcdefg")
     w = framing.lz4_decode_py(b)
     assert len(w) > 40_000
@@ -475,7 +475,7 @@ def test_compiled_ring_decoders(oracle):
     a 100 000-byte frame of a foreign writer (far matches beyond the LDS ring), a wrong frame check, malformed blocks"""
     import decode_kernel as dk
     import framing
-    import test_batch_decode_model as tm
+    import decoder_shapes as ds
     import xxhash
 
     def chk(b):
@@ -499,7 +499,7 @@ def test_compiled_ring_decoders(oracle):
     # chained sources
     cases = []
     for _ in range(4):
-        seqs = tm._chain_sequences(rng, int(rng.integers(50, 300)))
+        seqs = ds._chain_sequences(rng, int(rng.integers(50, 300)))
         b = framing.lz4_block([(rng.integers(0, 256, l).astype(np.uint8).tobytes(), o, m) for l, o, m in seqs], b"abcdefg")
         cases.append((b, framing.lz4_decode_py(b)))
     res, st, _ = dk.decode_blocks([(b, len(w)) for b, w in cases], fmt=0, kernel="ring", checks=[chk(w) for _, w in cases])
