@@ -149,12 +149,15 @@ enum {
                                     to 1024; larger values: S3S_E_UNSUPPORTED).  Since ABI 9 */
   S3S_OPT_PROFILE = 3,           /* 1: record per-stage HIP-event timings (s3s_stage_ms) */
   S3S_OPT_LZ4_VARIANT = 4,       /* tuning, identical output: 1 = general batch only (64 probes of the greedy
-                                    parse per step), 10 (default) = lean exact 64-byte windows in front of
+                                    parse per step), 10 = lean exact 64-byte windows in front of
                                     it (one candidate gather per window, several sequences per round trip),
+                                    11 (default) = 10 with the last 4 KiB of the input kept in LDS, from which
+                                    near match extensions are served (20 KiB of LDS per wavefront: 8 per CU),
                                     9 = auto: the context times 1 and 10 on its first large map outputs
                                     (1, 10, 1, 10), keeps the faster and re-measures the other every 32nd
-                                    call.  Other values are refused. */
-  S3S_OPT_LZ4_VARIANT_USED = 7,  /* read-only: the parse (1 or 10) the last LZ4 compress call ran */
+                                    call; a batched call (s3s_compress_map_outputs_batch*) has no timing
+                                    rounds and runs 11.  Other values are refused. */
+  S3S_OPT_LZ4_VARIANT_USED = 7,  /* read-only: the parse (1, 10 or 11) the last LZ4 compress call ran */
   S3S_OPT_SNAPPY_VARIANT = 6,    /* tuning, identical output: 0 = general batch only, 1 (default) = exact
                                     64-byte windows in front of it (several copies per round trip) */
   S3S_OPT_LZ4_DECODE_VARIANT = 5, /* tuning, identical output, LZ4 and Snappy: 4 (default) = batch decoder

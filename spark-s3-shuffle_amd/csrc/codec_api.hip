@@ -227,7 +227,8 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
       ctx->snappy_variant = (int)value;
       return S3S_OK;
     case S3S_OPT_LZ4_VARIANT:
-      if (value != 1 && value != 9 && value != 10) return fail(ctx, S3S_E_INVALID, "lz4 variant must be 1 (general batch), 10 (exact windows) or 9 (auto)");
+      if (value != 1 && value != 9 && value != 10 && value != 11)
+        return fail(ctx, S3S_E_INVALID, "lz4 variant must be 1 (general batch), 10 (exact windows), 11 (exact windows with the input ring) or 9 (auto)");
       ctx->lz4_variant = (int)value;
       ctx->auto_samples[0] = ctx->auto_samples[1] = 0;
       ctx->auto_tick = 0;
@@ -344,8 +345,17 @@ struct CompressCallScope {
   explicit CompressCallScope(const s3s_ctx* ctx) : n(g_compress_calls[ctx->device & 63]) { n.fetch_add(1, std::memory_order_relaxed); }
   ~CompressCallScope() { n.fetch_sub(1, std::memory_order_relaxed); }
 };
-static int lz4_resident_waves(const s3s_ctx* ctx) {
-  return (g_compress_calls[ctx->device & 63].load(std::memory_order_relaxed) > 1 ? 5 : 10) * ctx->cu_count;
+// The ring kernel (variant 11) has 20 KiB of LDS per wavefront: 8 per CU, 4 for each of two calls side by side.
+// (S3S_ABL_LDS_PAD, the occupancy experiment of lz4_compress.hip: the grid follows what 160 KiB of LDS per CU then holds,
+// 8 and 4 wavefronts per CU at a pad of 4096 — profiles/lz4_input_ring.md)
+#ifdef S3S_ABL_LDS_PAD
+static constexpr int kLz4WavesPerCu = (160 * 1024) / (16384 + S3S_ABL_LDS_PAD);
+#else
+static constexpr int kLz4WavesPerCu = 10;
+#endif
+static int lz4_resident_waves(const s3s_ctx* ctx, int variant) {
+  const int per_cu = variant == 11 ? 8 : kLz4WavesPerCu;
+  return (g_compress_calls[ctx->device & 63].load(std::memory_order_relaxed) > 1 ? per_cu / 2 : per_cu) * ctx->cu_count;
 }
 
 // Zstandard: workgroups of the persistent grid (zstd_compress.hip: ~43 KiB of LDS each, three per compute unit); the scratch
@@ -557,7 +567,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
       if (codec == S3S_CODEC_LZ4)
         launch_lz4_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint32_t>(ctx, B_ITEM_CHECK) + i0,
                             dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE) + i0, dev<uint32_t>(ctx, B_WORK),
-                            lz4_resident_waves(ctx), lz4_variant_run, ctx->stream,
+                            lz4_resident_waves(ctx, lz4_variant_run), lz4_variant_run, ctx->stream,
                             ctx->profile && i1 == n_items ? ctx->ev_hash : nullptr, bs >= kLz4U32From);
       else if (codec == S3S_CODEC_ZSTD)
         launch_zstd_compress(d_src, dev<Item>(ctx, B_ITEMS) + i0, i1 - i0, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
@@ -857,10 +867,12 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
   record(ctx, 0);
   // ---- ONE codec launch over every task's chunks ---------------------------------------------------------
   if (codec == S3S_CODEC_LZ4) {
-    const int variant = ctx->lz4_variant == 9 ? 10 : ctx->lz4_variant;
+    // (auto, 9, times 1 against 10 on the one-task entry points only; a batched call takes the windowed parse at once, and that
+    // is the ring kernel, which measured faster than variant 10 on TeraSort and on wide rows: profiles/lz4_input_ring.md)
+    const int variant = ctx->lz4_variant == 9 ? 11 : ctx->lz4_variant;
     ctx->lz4_variant_used = variant;
     launch_lz4_compress(base, d_items, n_items, dev<uint32_t>(ctx, B_ITEM_CHECK),
-                        dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), reinterpret_cast<uint32_t*>(d_plan + L.work), lz4_resident_waves(ctx),
+                        dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), reinterpret_cast<uint32_t*>(d_plan + L.work), lz4_resident_waves(ctx, variant),
                         variant, ctx->stream,
                         ctx->profile ? ctx->ev_hash : nullptr, bs >= kLz4U32From, /*work_is_zero=*/true);
   } else if (codec == S3S_CODEC_ZSTD) {

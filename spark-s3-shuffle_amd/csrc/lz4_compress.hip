@@ -17,8 +17,10 @@
 //       (ballot + ctz), lanes behind it undo their inserts.  Match extension is cooperative (256 B forward /
 //       64 B backward per memory round trip).  tests/model/lz4_wave_model.cpp proves that which lane wins a
 //       same-address LDS store is irrelevant.
-//   lean exact windows (kWindows = true, variant 10, default)  in front of the general batch: aligned 64-byte
+//   lean exact windows (kWindows = true, variant 10)  in front of the general batch: aligned 64-byte
 //       windows resolved with scalar mask arithmetic (see below; tests/model/lz4_window_model.cpp).
+//   the same with the input ring (variant 11, default: lz4_compress_ring.hip builds this file with S3S_LZ4_RING)  the last 4 KiB
+//       of the input behind the table in LDS (20 KiB -> 8 wavefronts per CU); near match extensions read it instead of memory.
 // Chunks of 65 547 bytes and more (S3S_OPT_LZ4_BLOCK_SIZE_LARGE, ABI 10) are another parse in liblz4 - byU32: 4096 x u32 table,
 // a 12-bit hash of FIVE bytes, candidates more than 65 535 bytes back passed over - and another instantiation here
 // (TabLdsU32, lz4_compress_u32_kernel: the general batch only; tests/model/lz4_wave_model_u32.cpp).  The host plan routes a
@@ -379,6 +381,10 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
 #if !defined(S3S_ENGINE_NO_DEFER)  // deferred emission: the waiting sequences' records (v118, v119), the flush's scratch, the record count
                            "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110",
                            "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "m0",
+#endif
+#ifdef S3S_LZ4_RING  // the ring's refill rows (two wavefronts per SIMD: 256 VGPRs are there)
+                           "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175", "v176", "v177", "v178", "v179", "v180",
+                           "v181", "v182", "v183",
 #endif
 #elif defined(S3S_ABL_DUP_PW) || defined(S3S_ABL_DUP_GATHER) || defined(S3S_ABL_DUP_IPSIDE)
                            "v160", "v161", "v162", "v163",
@@ -825,12 +831,21 @@ __device__ __forceinline__ uint32_t xxh32_wave(const uint8_t* g, int len, uint32
 }
 
 // ---- variant B: chunk read in place, only the table in LDS ----------------------------------
+// (lz4_compress_ring.hip builds this file once more with S3S_LZ4_RING: the same kernel under the name lz4_compress_ring_kernel,
+// with the window block's input ring behind the table — lz4_window_engine.inc — and nothing else of this file)
+#ifdef S3S_LZ4_RING
+#define lz4_compress_l2_kernel lz4_compress_ring_kernel
+#endif
 template <bool kWindows>
 __global__ __launch_bounds__(kWave) void lz4_compress_l2_kernel(
     const uint8_t* __restrict__ src_, const Item* __restrict__ items_, int32_t n_items_, int32_t slot_stride_,
     const uint32_t* __restrict__ item_check_, uint8_t* __restrict__ slots_,
     uint32_t* __restrict__ item_size_, uint32_t* __restrict__ work_) {  // (read through the kernarg segment, see the loop)
-#ifdef S3S_ABL_LDS_PAD  // occupancy experiment: fewer wavefronts per CU (timing only)
+#if defined(S3S_LZ4_RING)  // 16 KiB table, 4 KiB input ring behind it (written and read by the window block only)
+  // (S3S_ABL_LDS_PAD, the occupancy experiment below, does not apply here: this kernel's LDS is the table and the ring)
+  __shared__ __attribute__((aligned(16))) uint16_t table[8192 + 2048];
+  static_assert(sizeof(table) == 16384 + S3S_RING_BYTES, "the window block addresses the ring at LDS offset 16384");
+#elif defined(S3S_ABL_LDS_PAD)  // occupancy experiment: fewer wavefronts per CU (timing only)
   __shared__ __attribute__((aligned(16))) uint16_t table[8192 + S3S_ABL_LDS_PAD / 2];
 #else
   __shared__ __attribute__((aligned(16))) uint16_t table[8192];
@@ -915,6 +930,7 @@ __global__ __launch_bounds__(kWave) void lz4_compress_l2_kernel(
 // The same frame, slot and item_size as the kernel above, the general batch over the 4096 x u32 table.  No persistent
 // grid and no block touch: a chunk is 2 - 1024 times the 32 KiB one, so a launch per chunk is noise and a wavefront's
 // chunk no longer fits the share of L2 the touch was made for.  Items of every other kind are passed by.
+#ifndef S3S_LZ4_RING
 __global__ __launch_bounds__(kWave) void lz4_compress_u32_kernel(
     const uint8_t* __restrict__ src, const Item* __restrict__ items, int32_t n_items, int32_t slot_stride,
     const uint32_t* __restrict__ item_check, uint8_t* __restrict__ slots, uint32_t* __restrict__ item_size) {
@@ -943,6 +959,7 @@ __global__ __launch_bounds__(kWave) void lz4_compress_u32_kernel(
                                                                   item.len, slot + kSlotHeader, lane);
   finish_frame(slot, item.len, clen, check, item.kind >> 8, item_size + it, lane);
 }
+#endif  // !S3S_LZ4_RING
 
 
 // one wavefront per chunk, coalesced streaming (xxh32_wave): ~3x the 4-lanes-per-chunk kernel above.  kKind: the items it
@@ -1065,6 +1082,13 @@ __global__ __launch_bounds__(kWave) void xxh32_items_quad_kernel(
 
 }  // namespace
 
+#ifdef S3S_LZ4_RING
+void launch_lz4_compress_ring_kernel(const uint8_t* d_src, const Item* d_items, int32_t n_items, uint32_t* d_item_check, uint8_t* d_slots,
+                                     int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int grid, hipStream_t st) {
+  hipLaunchKernelGGL(lz4_compress_l2_kernel<true>, dim3((unsigned)grid), dim3(kWave), 0, st, d_src, d_items, n_items, slot_stride,
+                     d_item_check, d_slots, d_item_size, d_work);
+}
+#else
 void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                          uint32_t* d_item_check, uint8_t* d_slots, int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int resident_waves,
                          int variant, hipStream_t st, hipEvent_t after_hash, bool has_u32, bool work_is_zero) {
@@ -1098,7 +1122,9 @@ void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_it
   static const int grid_env = getenv("S3S_LZ4_GRID") ? atoi(getenv("S3S_LZ4_GRID")) : 0;  // (experiments)
   int grid = grid_env > 0 ? grid_env : resident_waves;
   if (grid > n_items) grid = n_items;
-  if (variant == 1)
+  if (variant == 11)  // the exact windows with the input ring (20 KiB of LDS: resident_waves is 8 or 4 per CU)
+    launch_lz4_compress_ring_kernel(d_src, d_items, n_items, d_item_check, d_slots, slot_stride, d_item_size, d_work, grid, st);
+  else if (variant == 1)
     hipLaunchKernelGGL(lz4_compress_l2_kernel<false>, dim3((unsigned)grid), dim3(kWave), 0, st, d_src,
                        d_items, n_items, slot_stride, d_item_check, d_slots, d_item_size, d_work);
   else
@@ -1109,5 +1135,6 @@ void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_it
     hipLaunchKernelGGL(lz4_compress_u32_kernel, dim3((unsigned)n_items), dim3(kWave), 0, st, d_src, d_items, n_items,
                        slot_stride, d_item_check, d_slots, d_item_size);
 }
+#endif  // !S3S_LZ4_RING
 
 }  // namespace s3s

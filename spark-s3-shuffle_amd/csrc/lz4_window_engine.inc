@@ -41,6 +41,184 @@
 #define S3S_ENGINE_DEFER 1
 #endif
 
+// ---- THE INPUT RING (-DS3S_LZ4_RING: lz4_compress_ring_kernel, S3S_OPT_LZ4_VARIANT 11) ---------------------------------------
+// The cooperative match extension is the last memory round trip on a window's chain (322 cycles alone, up to 1 180 behind other
+// wavefronts' gathers; an LDS read is ~100).  With this macro the wavefront keeps the last 4 KiB of its input in LDS behind the
+// table: the byte at chunk position q lies at LDS address 16384 + (q & 0xfff) (20 KiB per wavefront: eight per CU).
+//  * RING WRITE.  The stream dwords D (256 bytes from wbase + 124, loaded two windows ahead) go into the ring when they have
+//    arrived, at the end of the window's body; the one-window-skip and the far dispatch also write their D from wbase + 60.
+//    Invariant in window W's run loop: the ring holds [W + 316 - 4096, W + 316) (from W's end on [W + 380 - 4096, W + 380)).
+//    The ring's base is the DS offset field (no SGPR is left for it).
+//  * ENTRY / RE-ENTRY.  Every entry into the block and every dispatch that is not sequential or a one-window skip passes
+//    .Lw_dispf, which refills the ring from memory: the 4 KiB in front of W + 64 (four 1 KiB rows, addresses clamped at the
+//    chunk's start: a slot whose position would be negative holds anything and is never read), then D from W + 60.
+//  * VALIDITY.  "offset < S3S_RING_SPAN (3712)" is the whole test: the source side's aligned pairs start at src + 1 or later and
+//    its backward bytes reach src - 64, both inside the ring for such an offset (ip >= W: src - 64 >= W - 3776 > W + 316 - 4096); the ip side lies in it by
+//    construction.  AHEAD the ring holds 60 lanes' dwords (the pair of lane 59 ends at ip + 4 + 243 <= W + 63 + 247 < W + 316):
+//    lanes 60..63 are made equal, so a match that runs through all 240 covered bytes takes the "no mismatch" exit (hand-back,
+//    code 2: the C++ loop extends it from memory; with the global loads that exit is at 256 bytes, so matches of 244 .. 259
+//    bytes from a near source are handed back now and cost a refill on re-entry: none in the benchmarked workloads, see
+//    DESIGN.md section 6).  Any other offset takes the global loads unchanged.  The constants and the inequalities between them
+//    stand next to S3S_RING_SPAN below, checked when the file is compiled.
+//  * UNALIGNED READS.  A ds_read_b32 that is not dword-aligned is served lane by lane (65 cycles, tools/probe/lds_align_probe.hip)
+//    and could not wrap; each side reads the ALIGNED PAIR around its dword instead (addresses masked per lane, so the ring's
+//    wrap point needs neither a mirror margin nor a split read) and one v_alignbyte_b32 shifts it (the shift is the low two
+//    bits of ip / of the candidate, taken by the instruction itself).
+//  * THE EARLY ISSUE STAYS ON GLOBAL LOADS.  S3S_ENGINE_SPEC_COMMIT issues the next window's first extension while commit, table
+//    read and dispatch run: its latency is off the chain already, and taking it from the ring put an LDS wait and ~18 instructions
+//    ON the chain of every window (model: + 96 K cycles per TeraSort block against 118 K saved; measured: no gain, profiles/lz4_input_ring.md).  Only its
+//    backward part (.Lw_extbx) comes from the ring.
+//  * ORDER OF RETURNS.  LDS reads and global loads return independently, and an early extension the run loop passed by may still
+//    be landing in v130 / v131: the ring path keeps its forward data in v150 / v151 (pairs' high dwords in v125 / v126, whose
+//    role as load addresses ended at issue) and compares there.  Ring reads are always waited for (lgkmcnt(0)) at once.
+#ifdef S3S_LZ4_RING
+#if !defined(S3S_ENGINE_SPEC) || !defined(S3S_ENGINE_DEFER) || defined(S3S_ENGINE_PW_DIRECT) || defined(S3S_ENGINE_DLOAD_20)
+#error "S3S_LZ4_RING is built on the shipped block (speculative gather, deferred emission, 64-lane stream load)"
+#endif
+#define S3S_RING_SPAN "0xe80"
+/* the same constants as numbers, and what ties them together.  Assumptions: s76 (the window's base) is a multiple of 64 in chunk
+   positions, so the ring's ds_write_b32 / ds_write_b128 are aligned to their width and no access straddles ring address 0xfff;
+   an extension's ip is >= s76 (event lanes are lanes of the window); D reaches S3S_RING_AHEAD bytes behind s76 when the run loop
+   of s76 runs (60 + 256, S3S_PW_DLOAD("60") / the previous window's S3S_PW_DLOAD("124")).
+     behind: the lowest byte read is src - 64 (backward part) with src = ip - offset >= s76 - (SPAN - 1), and the ring's lowest
+             position is s76 + AHEAD - BYTES:   SPAN - 1 + 64 + AHEAD <= BYTES   (3711 + 64 + 316 = 4091: five bytes to spare)
+     ahead:  lane 59's aligned pair ends below ip + 4 + 4 * 59 + 8 <= s76 + 63 + 248:   63 + 248 <= AHEAD */
+#define S3S_RING_BYTES 4096
+#define S3S_RING_SPAN_N 0xe80
+#define S3S_RING_AHEAD 316
+#define S3S_RING_LANES 60
+#if S3S_RING_SPAN_N - 1 + 64 + S3S_RING_AHEAD > S3S_RING_BYTES || 63 + 4 + 4 * (S3S_RING_LANES - 1) + 8 > S3S_RING_AHEAD
+#error "S3S_RING_SPAN / S3S_RING_LANES no longer fit what the ring holds behind and ahead of a window"
+#endif
+#define S3S_RING_WRITE(OFF) /* v154 = D from s76 + OFF (v158 = s76 + 4 * lane) -> the ring */                 \
+  "v_add_u32_e32 v158, " OFF ", v158\n\t"                                                                  \
+  "v_and_b32_e32 v158, 0xfff, v158\n\t"                                                                    \
+  "ds_write_b32 v158, v154 offset:16384\n\t"
+#define S3S_RING_FILL_ISSUE /* the 4 KiB in front of s76 + 64: lane L takes 16 bytes of each 1 KiB row */      \
+  "v_lshl_add_u32 v150, v129, 4, s76\n\t"                                                                  \
+  "v_add_u32_e32 v151, 0xfffff040, v150\n\t"                                                               \
+  "v_add_u32_e32 v152, 0xfffff440, v150\n\t"                                                               \
+  "v_add_u32_e32 v153, 0xfffff840, v150\n\t"                                                               \
+  "v_add_u32_e32 v150, 0xfffffc40, v150\n\t"                                                               \
+  "v_max_i32_e32 v151, 0, v151\n\t"                                                                        \
+  "v_max_i32_e32 v152, 0, v152\n\t"                                                                        \
+  "v_max_i32_e32 v153, 0, v153\n\t"                                                                        \
+  "v_max_i32_e32 v150, 0, v150\n\t"                                                                        \
+  "global_load_dwordx4 v[168:171], v151, %[inp]\n\t"                                                       \
+  "global_load_dwordx4 v[172:175], v152, %[inp]\n\t"                                                       \
+  "global_load_dwordx4 v[176:179], v153, %[inp]\n\t"                                                       \
+  "global_load_dwordx4 v[180:183], v150, %[inp]\n\t"
+#define S3S_RING_FILL_WRITE /* (after vmcnt(0)) */                                                            \
+  "v_lshl_add_u32 v150, v129, 4, s76\n\t"                                                                  \
+  "v_add_u32_e32 v151, 64, v150\n\t"                                                                       \
+  "v_add_u32_e32 v152, 0x440, v150\n\t"                                                                    \
+  "v_add_u32_e32 v153, 0x840, v150\n\t"                                                                    \
+  "v_add_u32_e32 v150, 0xc40, v150\n\t"                                                                    \
+  "v_and_b32_e32 v151, 0xfff, v151\n\t"                                                                    \
+  "v_and_b32_e32 v152, 0xfff, v152\n\t"                                                                    \
+  "v_and_b32_e32 v153, 0xfff, v153\n\t"                                                                    \
+  "v_and_b32_e32 v150, 0xfff, v150\n\t"                                                                    \
+  "ds_write_b128 v151, v[168:171] offset:16384\n\t"                                                        \
+  "ds_write_b128 v152, v[172:175] offset:16384\n\t"                                                        \
+  "ds_write_b128 v153, v[176:179] offset:16384\n\t"                                                        \
+  "ds_write_b128 v150, v[180:183] offset:16384\n\t"
+/* v125 / v126 = the byte positions of every lane's ip-side / source-side dword -> the aligned pairs (v150, v125) / (v151, v126) */
+#define S3S_RING_ISSUE                                                                                        \
+  "v_and_b32_e32 v150, 0xffc, v125\n\t"                                                                    \
+  "v_add_u32_e32 v125, 4, v125\n\t"                                                                        \
+  "v_and_b32_e32 v151, 0xffc, v126\n\t"                                                                    \
+  "v_add_u32_e32 v126, 4, v126\n\t"                                                                        \
+  "v_and_b32_e32 v125, 0xffc, v125\n\t"                                                                    \
+  "v_and_b32_e32 v126, 0xffc, v126\n\t"                                                                    \
+  "ds_read_b32 v150, v150 offset:16384\n\t"                                                                \
+  "ds_read_b32 v151, v151 offset:16384\n\t"                                                                \
+  "ds_read_b32 v125, v125 offset:16384\n\t"                                                                \
+  "ds_read_b32 v126, v126 offset:16384\n\t"
+/* the pairs are back: shift (by the low two bits of ip = s89 / of the candidate = s88), lanes 60..63 equal; then the forward
+   compare of .Lw_fwcmp / .Lw_extb on v150 / v151 (NOT v130 / v131: an early extension the run loop passed by may still be landing there) */
+#define S3S_RING_FIN                                                                                          \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
+  "s_lshr_b64 s[84:85], -1, 4\n\t"                                                                         \
+  "v_alignbyte_b32 v150, v125, v150, s89\n\t"                                                              \
+  "v_alignbyte_b32 v151, v126, v151, s88\n\t"                                                              \
+  "v_cndmask_b32_e64 v151, v150, v151, s[84:85]\n\t"                                                       \
+  "v_cmp_ne_u32_e64 s[82:83], v150, v151\n\t"
+/* the backward bytes (up to 64 in front of ip and of the source) from the ring */
+#define S3S_RING_BWD                                                                                          \
+  "s_min_i32 s99, s92, s88\n\t"                                                                            \
+  "v_mov_b32_e32 v127, 0\n\t"                                                                              \
+  "v_mov_b32_e32 v128, 1\n\t"                                                                              \
+  "v_cmp_gt_i32_e64 s[82:83], s99, v129\n\t"                                                               \
+  "s_add_i32 s97, s89, -1\n\t"                                                                             \
+  "s_add_i32 s98, s88, -1\n\t"                                                                             \
+  "s_and_saveexec_b64 s[84:85], s[82:83]\n\t"                                                              \
+  "v_sub_u32_e32 v123, s97, v129\n\t"                                                                      \
+  "v_sub_u32_e32 v124, s98, v129\n\t"                                                                      \
+  "v_and_b32_e32 v123, 0xfff, v123\n\t"                                                                    \
+  "v_and_b32_e32 v124, 0xfff, v124\n\t"                                                                    \
+  "ds_read_u8 v127, v123 offset:16384\n\t"                                                                 \
+  "ds_read_u8 v128, v124 offset:16384\n\t"                                                                 \
+  "s_mov_b64 exec, s[84:85]\n\t"
+/* .Lw_ext, v125 / v126 / s98 = offset set: a source inside the span is served here, anything else falls through */
+#define S3S_RING_EXT(NB)                                                                                      \
+  "s_cmpk_lt_u32 s98, " S3S_RING_SPAN "\n\t"                                                               \
+  "s_cbranch_scc0 .Lw_extg" NB "_%=\n\t"                                                                   \
+  S3S_RING_ISSUE                                                                                           \
+  "s_and_b32 s97, s87, 0xc00000\n\t"                                                                       \
+  "s_cbranch_scc1 .Lw_mfullr" NB "_%=\n\t"                                                                 \
+  ".Lw_fwonlyr" NB "_%=:\n\t"                                                                              \
+  S3S_RING_FIN                                                                                             \
+  "v_xor_b32_e32 v123, v150, v151\n\t"                                                                     \
+  "s_branch .Lw_fwc2" NB "_%=\n\t"                                                                        \
+  ".Lw_mfullr" NB "_%=:\n\t"                                                                               \
+  "s_bitcmp1_b32 s87, 23\n\t"                                                                              \
+  "s_cbranch_scc1 .Lw_extbr" NB "_%=\n\t"                                                                  \
+  "s_cmp_gt_i32 s92, 4\n\t"                                                                                \
+  "s_cbranch_scc0 .Lw_fwonlyr" NB "_%=\n\t"                                                                \
+  ".Lw_extbr" NB "_%=:\n\t"                                                                                \
+  S3S_RING_BWD                                                                                             \
+  S3S_RING_FIN                                                                                             \
+  "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
+  "v_xor_b32_e32 v123, v150, v151\n\t"                                                                     \
+  "s_branch .Lw_extbc2" NB "_%=\n\t"                                                                        \
+  /* the early extension (global loads into v130 / v131: vmcnt(2), see .Lw_exth) needs its backward part */  \
+  ".Lw_mfullx" NB "_%=:\n\t"                                                                               \
+  "s_bitcmp1_b32 s87, 23\n\t"                                                                              \
+  "s_cbranch_scc1 .Lw_extbx" NB "_%=\n\t"                                                                  \
+  "s_cmp_gt_i32 s92, 4\n\t"                                                                                \
+  "s_cbranch_scc0 .Lw_exthw" NB "_%=\n\t"                                                                  \
+  ".Lw_extbx" NB "_%=:\n\t"                                                                                \
+  "s_sub_i32 s98, s89, s88\n\t"                                                                            \
+  "s_cmpk_lt_u32 s98, " S3S_RING_SPAN "\n\t"                                                               \
+  "s_cbranch_scc0 .Lw_extb" NB "_%=\n\t"                                                                   \
+  S3S_RING_BWD                                                                                             \
+  "s_waitcnt vmcnt(2) lgkmcnt(0)\n\t"                                                                      \
+  "s_branch .Lw_extbc" NB "_%=\n\t"                                                                        \
+  ".Lw_extg" NB "_%=:\n\t"
+#define S3S_RING_EXTFULL(NB)                                                                                  \
+  "s_cmpk_lt_u32 s98, " S3S_RING_SPAN "\n\t"                                                               \
+  "s_cbranch_scc0 .Lw_extfg" NB "_%=\n\t"                                                                  \
+  S3S_RING_ISSUE                                                                                           \
+  "s_branch .Lw_extbr" NB "_%=\n\t"                                                                        \
+  ".Lw_extfg" NB "_%=:\n\t"
+#define S3S_RING_EXTBC(NB) ".Lw_extbc" NB "_%=:\n\t"
+#define S3S_RING_EXTBC2(NB) ".Lw_extbc2" NB "_%=:\n\t"
+#define S3S_RING_FWC2(NB) ".Lw_fwc2" NB "_%=:\n\t"
+#define S3S_RING_EXTH_MFULL(NB) "s_cbranch_scc1 .Lw_mfullx" NB "_%=\n\t"
+#define S3S_RING_EXTHW(NB) ".Lw_exthw" NB "_%=:\n\t"
+#else
+#define S3S_RING_WRITE(OFF)
+#define S3S_RING_FILL_ISSUE
+#define S3S_RING_FILL_WRITE
+#define S3S_RING_EXT(NB)
+#define S3S_RING_EXTFULL(NB)
+#define S3S_RING_EXTBC(NB)
+#define S3S_RING_EXTBC2(NB)
+#define S3S_RING_FWC2(NB)
+#define S3S_RING_EXTH_MFULL(NB) "s_cbranch_scc1 .Lw_mfull" NB "_%=\n\t"
+#define S3S_RING_EXTHW(NB)
+#endif
+
 #ifdef S3S_ENGINE_ABL_NOSTORE  // timing experiment only (wrong output): what do the sequence stores cost?
 #define S3S_ENGINE_STORE ""
 #else
@@ -160,14 +338,18 @@
   S3S_PW_ALIGN(Z0, Z1, Z2, Z3)                                                                             \
   S3S_PW_DLOAD("60")                                                                                       \
   "s_waitcnt vmcnt(0)\n\t"                                                                                 \
+  S3S_RING_WRITE("60")                                                                                     \
   S3S_PW_PERM                                                                                              \
   "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
   S3S_PW_DLOAD("124")
 /* anything else: pw0 by a direct load (issued by the caller of this macro), pw1 and pw2 through D */
 #define S3S_ENGINE_DISP_FAR(Y, Z)                                                                              \
+  S3S_RING_FILL_ISSUE                                                                                      \
   "global_load_dword %[vp], v148, %[inp] offset:-64\n\t"                                                   \
   S3S_PW_DLOAD("60")                                                                                       \
   "s_waitcnt vmcnt(0)\n\t"                                                                                 \
+  S3S_RING_FILL_WRITE                                                                                      \
+  S3S_RING_WRITE("60")                                                                                     \
   S3S_PW_PERM                                                                                              \
   "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
   S3S_PW_DLOAD("124")
@@ -319,7 +501,7 @@
 #define S3S_ENGINE_SPEC_DUP(NB)
 #define S3S_ENGINE_SPEC_X2(NB)
 #define S3S_ENGINE_SPEC_EXT(NB)
-#define S3S_ENGINE_SPEC_EXTFULL
+#define S3S_ENGINE_SPEC_EXTFULL(NB)
 #define S3S_ENGINE_SPEC_FWCMP(NB)
 #define S3S_ENGINE_SPEC_NOEV(NB)
 #define S3S_ENGINE_SPEC_COMMIT(NB, Z0, Z1, Z2, Z3, N0, N1, N2, N3)
@@ -345,6 +527,11 @@
 //               [D load, spec gather] -> vmcnt(0) (.Lw_noev with K == 0);
 //   .Lw_exth    [ext a, ext b, D load of the dispatch, spec gather issued at the head (, stores)] -> vmcnt(2);
 //   .Lw_winm    [D load, gather, next spec gather] -> vmcnt(1).
+// With S3S_LZ4_RING the same counts hold: the ring paths issue LDS accesses only and wait for them with lgkmcnt(0) at once
+// (every LDS wait of the block is lgkmcnt(0), so the ring's writes never change a count); the refill's four row loads go out
+// in .Lw_dispf in front of the D load and are covered by that dispatch's vmcnt(0); the ring write at a window's end sits behind
+// the window-end vmcnt(0), which is what makes D valid; .Lw_extbx (backward part of the early extension from the ring) keeps
+// .Lw_exth's vmcnt(2) for the forward loads and adds lgkmcnt(0).
 #ifdef S3S_ENGINE_PW_DIRECT
 #error "S3S_ENGINE_SPEC needs the permuted stream load"
 #endif
@@ -455,7 +642,8 @@
   /* the first extension of this window was issued at the end of the previous one: only wait for it */     \
   ".Lw_exth" NB "_%=:\n\t"                                                                                 \
   "s_and_b32 s97, s87, 0xc00000\n\t"                                                                       \
-  "s_cbranch_scc1 .Lw_mfull" NB "_%=\n\t"                                                                  \
+  S3S_RING_EXTH_MFULL(NB)                                                                                  \
+  S3S_RING_EXTHW(NB)                                                                                       \
   "s_waitcnt vmcnt(2)\n\t"                                                                                 \
   "s_branch .Lw_fwcmp" NB "_%=\n\t"                                                                        \
   S3S_ENGINE_NVW(NB)
@@ -478,7 +666,7 @@
   "s_cmp_eq_u32 s86, %[code]\n\t"                                                                          \
   "s_mov_b32 %[code], -1\n\t"                                                                              \
   "s_cbranch_scc1 .Lw_exth" NB "_%=\n\t"
-#define S3S_ENGINE_SPEC_EXTFULL "s_mov_b32 %[code], -1\n\t"
+#define S3S_ENGINE_SPEC_EXTFULL(NB) "s_mov_b32 %[code], -1\n\t"
 #define S3S_ENGINE_SPEC_FWCMP(NB) ".Lw_fwcmp" NB "_%=:\n\t"
 /* .Lw_noev: scc = (K != 0) = a sequence was emitted in this window */
 #ifdef S3S_ENGINE_DEFER /* no sequence stores in the run loop: the next window's gather is always the youngest access */
@@ -508,6 +696,7 @@
    Z), and the extension of its first live matching lane when the record says it will need one */
 #define S3S_ENGINE_SPEC_COMMIT(NB, Z0, Z1, Z2, Z3, N0, N1, N2, N3)                                              \
   S3S_ENGINE_WEND_VMCNT                                                                                    \
+  S3S_RING_WRITE("124")                                                                                    \
   "v_cmp_gt_u32_e32 vcc, 4, v159\n\t"                                                                      \
   S3S_ENGINE_INFO(Z0, Z1, Z2, Z3, N0, N1, N2, N3, "v159", "")                                               \
   S3S_ENGINE_PF_MASK                                                                                       \
@@ -904,6 +1093,7 @@
   "v_lshl_add_u32 v125, v129, 2, s97\n\t"                                                                  \
   "s_sub_i32 s98, s89, s88\n\t"                                                                            \
   "v_subrev_u32_e32 v126, s98, v125\n\t"                                                                   \
+  S3S_RING_EXT(NB)                                                                                         \
   "global_load_dword v130, v125, %[inp]\n\t"                                                               \
   S3S_ENGINE_ABL_DUP_IPSIDE                                                                                \
   "global_load_dword v131, v126, %[inp]\n\t"                                                               \
@@ -914,6 +1104,7 @@
   S3S_ENGINE_SPEC_FWCMP(NB)                                                                                \
   "v_cmp_ne_u32_e64 s[82:83], v130, v131\n\t"                                                              \
   "v_xor_b32_e32 v123, v130, v131\n\t"                                                                     \
+  S3S_RING_FWC2(NB)                                                                                        \
   "s_cmp_eq_u64 s[82:83], 0\n\t"                                                                           \
   "s_cbranch_scc1 .Lw_x2" NB "_%=\n\t"                                                                     \
   "s_ff1_i32_b64 s98, s[82:83]\n\t"                                                                        \
@@ -958,11 +1149,12 @@
   "s_cbranch_scc0 .Lw_fwonly" NB "_%=\n\t"                                                                 \
   "s_branch .Lw_extb" NB "_%=\n\t"                                                                         \
   ".Lw_extfull" NB "_%=:\n\t"                                                                              \
-  S3S_ENGINE_SPEC_EXTFULL                                                                                  \
+  S3S_ENGINE_SPEC_EXTFULL(NB)                                                                              \
   "s_add_i32 s97, s89, 4\n\t"                                                                              \
   "v_lshl_add_u32 v125, v129, 2, s97\n\t"                                                                  \
   "s_sub_i32 s98, s89, s88\n\t"                                                                            \
   "v_subrev_u32_e32 v126, s98, v125\n\t"                                                                   \
+  S3S_RING_EXTFULL(NB)                                                                                     \
   "global_load_dword v130, v125, %[inp]\n\t"                                                               \
   S3S_ENGINE_ABL_DUP_IPSIDE                                                                                \
   "global_load_dword v131, v126, %[inp]\n\t"                                                               \
@@ -980,9 +1172,11 @@
   "global_load_ubyte v128, v124, %[inp]\n\t"                                                               \
   "s_mov_b64 exec, s[84:85]\n\t"                                                                           \
   "s_waitcnt vmcnt(0)\n\t"                                                                                 \
+  S3S_RING_EXTBC(NB)                                                                                       \
   "v_cmp_ne_u32_e64 s[82:83], v130, v131\n\t"                                                              \
   "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
   "v_xor_b32_e32 v123, v130, v131\n\t"                                                                     \
+  S3S_RING_EXTBC2(NB)                                                                                      \
   "s_ff1_i32_b64 s97, s[84:85]\n\t"                                                                        \
   "s_min_u32 s97, s97, 63\n\t"                                                                             \
   "s_cmp_eq_u32 s97, 63\n\t"                                                                               \

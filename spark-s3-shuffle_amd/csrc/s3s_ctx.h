@@ -50,7 +50,7 @@ struct s3s_ctx {
   int64_t lz4_block = 32768;
   int64_t snappy_block = 32768;
   int profile = 0;
-  int lz4_variant = 10;  // 10 = lean exact windows (default); 1 = general batch; 9 = auto: the context times both on its own calls
+  int lz4_variant = 11;  // 11 = exact windows with the input ring (default); 10 = exact windows; 1 = general batch; 9 = auto: the context times 1 and 10 on its own one-task calls (batched calls run 11)
   // auto-tuning state (S3S_OPT_LZ4_VARIANT = 9): index 0 = variant 1 (general batch), 1 = variant 10
   // (exact windows).  Shuffle data of one stage has one schema, so the faster parse for a
   // context's first map outputs stays the faster one; every 32nd large call re-measures the other.

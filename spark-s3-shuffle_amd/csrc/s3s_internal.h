@@ -92,6 +92,9 @@ constexpr uint32_t kRawFlag = 0x80000000u;
 void launch_lz4_compress(const uint8_t* d_src, const Item* d_items, int32_t n_items,
                          uint32_t* d_item_check, uint8_t* d_slots, int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int resident_waves,
                          int variant, hipStream_t st, hipEvent_t after_hash = nullptr, bool has_u32 = false, bool work_is_zero = false);
+//   variant 11 (lz4_compress_ring.hip): the exact-window kernel with the input ring, launched by launch_lz4_compress
+void launch_lz4_compress_ring_kernel(const uint8_t* d_src, const Item* d_items, int32_t n_items, uint32_t* d_item_check, uint8_t* d_slots,
+                                     int32_t slot_stride, uint32_t* d_item_size, uint32_t* d_work, int grid, hipStream_t st);
 // Snappy: same for kItemSnappyChunk.
 bool snappy_compress_available();
 //   slot_stride: bytes between slots (a raw snappy block can be larger than its chunk)
