@@ -275,7 +275,8 @@ __device__ __forceinline__ uint32_t probe_hash(uint32_t v, uint32_t b4) {
 //                                       in the table yet)
 //     Dp    ⊇ lanes that share their hash with an earlier lane of the window (found with two
 //             speculative store passes that are rolled back; which lane wins a same-address
-//             store only decides which superset we get)
+//             store only decides which superset we get; the hand-written block runs them one window early over all 64
+//             lanes, so its Dp also holds live lanes that share their hash with a DEAD lane only: still a superset)
 //     Ecp   = lanes whose table candidate matches, with per-lane forward length (<= 64) and
 //             backward equal count (<= 8) loaded and computed speculatively
 //   and then resolved run by run with SCALAR mask arithmetic only.  K collects what the
@@ -358,6 +359,11 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
           if ((uint32_t)reinterpret_cast<uintptr_t>(T.t) == 0u) {  // (the block addresses the table at LDS offset 0)
             // Whole windows in one hand-written gfx950 block (lz4_window_engine.inc): it returns at a window
             // boundary (codes 0, 3, 4) or at the first event it does not handle (code 2: the loop below resumes there).
+            // What it hands over with code 2: the table holds real candidates (the block rolls the next window's passes back
+            // before it leaves), and Dp may flag a live lane whose only hash partners are DEAD lanes of the window (the block's
+            // passes run over all 64 lanes, one window early): the loop below finds no kept / in-run lane for it (dh == 0) and
+            // goes on with the table candidate, and the commit's `K & Dp` test at worst runs one read-back that changes nothing.
+            // With code 0 Dp is the NEXT window's (all lanes) and is not used: the preparation below computes its own.
             int code, putp = __builtin_amdgcn_readfirstlane(put_pending ? 1 : 0);
             const int base_in = base;
             uint32_t vput_s = __builtin_amdgcn_readfirstlane(vput);
@@ -379,6 +385,8 @@ __device__ int lz4_compress_wave(const Src in, const Tab T, int len, uint8_t* ou
 #if !defined(S3S_ENGINE_NO_SPEC)  // speculative next-window gather: two more gather register sets, cpS, the next window's hash
                            "v155", "v156", "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167",
 #if !defined(S3S_ENGINE_NO_DEFER)  // deferred emission: the waiting sequences' records (v118, v119), the flush's scratch, the record count
+                           // (v115 - v117 of that scratch also carry the NEXT window's duplicate-hash passes across the run loop,
+                           // S3S_ENGINE_DUP_AHEAD: the block switches that off by itself in a build without this list)
                            "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110",
                            "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "m0",
 #endif

@@ -41,6 +41,46 @@
 #define S3S_ENGINE_DEFER 1
 #endif
 
+// THE NEXT WINDOW'S DUPLICATE PASSES RUN DURING THIS WINDOW (round 7).  Dp of window W + 64 depends only on its lanes' hashes,
+// and those (v155 / v156) exist at W's head.  The head used to run W's own two passes - two dependent LDS round trips, the
+// second with only the run-loop state in its shadow - before the run loop could start, because ED needs Dp.  Now W's head
+// issues pass 1 of W + 64 next to the speculative table read it waits for anyway, issues pass 2 and goes into the run loop;
+// pass 2's answer is looked at in .Lw_commit, where it has long arrived.  Its live lanes are not known yet, so the passes run
+// over all 64 lanes: Dp is the set of lanes that share their hash with ANY lane of the window, restricted to the live lanes at
+// the next head - a superset of the old one.  A lane that is in it only because of a dead partner resolves as before
+// (.Lw_dup finds no kept / in-run lane -> .Lw_dupnone; the C++ loop does the same with a handed-back Dp).
+//   v117 position of the next window's lanes   v116 / v115 what pass 1 / pass 2 read back   (the flush's scratch: the flush
+//   runs at a window's end behind the commit and at an exit behind .Lw_x2, where these are dead)
+// ORDER ON THE TABLE (the LDS returns and applies one wavefront's accesses in order):  between W's head and its commit the
+// slots of W + 64's hashes hold positions of W + 64, not candidates, and nothing reads the table there: the run loop, .Lw_fix
+// and .Lw_regather work on the cp register.  The roll-back (the slot's holder after pass 2 writes cpS = v159, which W's head
+// read IN FRONT of pass 1) is the first LDS access of .Lw_commit, so it lies in front of the commit's own store (a slot both
+// write keeps the commit's position), of the ip-2 put behind the commit (.Lw_pendset / S3S_ENGINE_PEND_NEXT), of the fresh table
+// read of W + 64, of .Lw_cfix and of every hand-back at a window boundary (code 0) and every dispatch (sequential, skip, far,
+// same): all of them see real candidates.  The one exit in mid-window (.Lw_x2, code 2) rolls back itself.  A window entered
+// through .Lw_winm runs its own passes as before (the table is real then) and the next window's behind them.
+// Needs the deferred emission (its register list has v115 - v117).  -DS3S_ENGINE_NO_DUP_AHEAD builds the round-6 head (A/B, tests).
+#if defined(S3S_ENGINE_NO_DUP_AHEAD) || !defined(S3S_ENGINE_DEFER)
+#undef S3S_ENGINE_DUP_AHEAD
+#elif !defined(S3S_ENGINE_DUP_AHEAD)
+#define S3S_ENGINE_DUP_AHEAD 1
+#endif
+
+// Layout (round 7): a taken branch costs ~25 cycles beyond its issue (profiles/r05_experiments.md §5) and the block's common
+// paths were entered and left by one: same instructions, other order, chosen from the taken-branch column per label of
+// tests/tools/chain_profile.py (profiles/lz4_chain.md §1 lists it before and after).
+//  * .Lw_leave (the exit of 0.9 windows in 1.0) stands directly in front of the commit and falls into it; the rare .Lw_noev
+//    (~50 per block) stands in front of it and jumps over it.
+//  * .Lw_ext: the wait for the extension that is already in flight (.Lw_exth; 63 % of a TeraSort block's extensions) is the
+//    fall-through and falls into the compare (.Lw_fwcmp); the on-demand extension (.Lw_extd) is the branch and jumps back.
+//  * (ring) .Lw_extbr stands in line behind .Lw_extfull's ring issue and falls into .Lw_extbc2, see S3S_RING_EXTFULL.
+// -DS3S_ENGINE_LAYOUT_R6 builds the round-6 order (A/B, tests).
+#if defined(S3S_ENGINE_LAYOUT_R6)
+#undef S3S_ENGINE_LAYOUT
+#elif !defined(S3S_ENGINE_LAYOUT)
+#define S3S_ENGINE_LAYOUT 1
+#endif
+
 // ---- THE INPUT RING (-DS3S_LZ4_RING: lz4_compress_ring_kernel, S3S_OPT_LZ4_VARIANT 11) ---------------------------------------
 // The cooperative match extension is the last memory round trip on a window's chain (322 cycles alone, up to 1 180 behind other
 // wavefronts' gathers; an LDS read is ~100).  With this macro the wavefront keeps the last 4 KiB of its input in LDS behind the
@@ -175,12 +215,7 @@
   "s_cbranch_scc1 .Lw_extbr" NB "_%=\n\t"                                                                  \
   "s_cmp_gt_i32 s92, 4\n\t"                                                                                \
   "s_cbranch_scc0 .Lw_fwonlyr" NB "_%=\n\t"                                                                \
-  ".Lw_extbr" NB "_%=:\n\t"                                                                                \
-  S3S_RING_BWD                                                                                             \
-  S3S_RING_FIN                                                                                             \
-  "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
-  "v_xor_b32_e32 v123, v150, v151\n\t"                                                                     \
-  "s_branch .Lw_extbc2" NB "_%=\n\t"                                                                        \
+  S3S_RING_EXTBR_HERE(NB)                                                                                  \
   /* the early extension (global loads into v130 / v131: vmcnt(2), see .Lw_exth) needs its backward part */  \
   ".Lw_mfullx" NB "_%=:\n\t"                                                                               \
   "s_bitcmp1_b32 s87, 23\n\t"                                                                              \
@@ -195,12 +230,37 @@
   "s_waitcnt vmcnt(2) lgkmcnt(0)\n\t"                                                                      \
   "s_branch .Lw_extbc" NB "_%=\n\t"                                                                        \
   ".Lw_extg" NB "_%=:\n\t"
+#ifdef S3S_ENGINE_LAYOUT
+/* (layout: .Lw_extbr is entered from .Lw_extfull - the duplicate-hash path - in 30 of 30 TeraSort and 276 of 277 wide-row
+   visits per block: it stands in line there and falls into .Lw_extbc2; the global-load form of .Lw_extfull / .Lw_extb is the
+   one that stands out of line, S3S_ENGINE_EXTB_OUTLINE) */
+#define S3S_RING_EXTBR_HERE(NB) "s_branch .Lw_extbr" NB "_%=\n\t"
+#define S3S_RING_EXTFULL(NB)                                                                                  \
+  "s_cmpk_lt_u32 s98, " S3S_RING_SPAN "\n\t"                                                               \
+  "s_cbranch_scc0 .Lw_extfg" NB "_%=\n\t"                                                                  \
+  S3S_RING_ISSUE                                                                                           \
+  ".Lw_extbr" NB "_%=:\n\t"                                                                                \
+  S3S_RING_BWD                                                                                             \
+  S3S_RING_FIN                                                                                             \
+  "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
+  "v_xor_b32_e32 v123, v150, v151\n\t"
+#define S3S_RING_EXTFG(NB) ".Lw_extfg" NB "_%=:\n\t"
+#else
+#define S3S_RING_EXTBR_HERE(NB)                                                                               \
+  ".Lw_extbr" NB "_%=:\n\t"                                                                                \
+  S3S_RING_BWD                                                                                             \
+  S3S_RING_FIN                                                                                             \
+  "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
+  "v_xor_b32_e32 v123, v150, v151\n\t"                                                                     \
+  "s_branch .Lw_extbc2" NB "_%=\n\t"
 #define S3S_RING_EXTFULL(NB)                                                                                  \
   "s_cmpk_lt_u32 s98, " S3S_RING_SPAN "\n\t"                                                               \
   "s_cbranch_scc0 .Lw_extfg" NB "_%=\n\t"                                                                  \
   S3S_RING_ISSUE                                                                                           \
   "s_branch .Lw_extbr" NB "_%=\n\t"                                                                        \
   ".Lw_extfg" NB "_%=:\n\t"
+#define S3S_RING_EXTFG(NB)
+#endif
 #define S3S_RING_EXTBC(NB) ".Lw_extbc" NB "_%=:\n\t"
 #define S3S_RING_EXTBC2(NB) ".Lw_extbc2" NB "_%=:\n\t"
 #define S3S_RING_FWC2(NB) ".Lw_fwc2" NB "_%=:\n\t"
@@ -212,6 +272,7 @@
 #define S3S_RING_FILL_WRITE
 #define S3S_RING_EXT(NB)
 #define S3S_RING_EXTFULL(NB)
+#define S3S_RING_EXTFG(NB)
 #define S3S_RING_EXTBC(NB)
 #define S3S_RING_EXTBC2(NB)
 #define S3S_RING_FWC2(NB)
@@ -532,6 +593,11 @@
 // in .Lw_dispf in front of the D load and are covered by that dispatch's vmcnt(0); the ring write at a window's end sits behind
 // the window-end vmcnt(0), which is what makes D valid; .Lw_extbx (backward part of the early extension from the ring) keeps
 // .Lw_exth's vmcnt(2) for the forward loads and adds lgkmcnt(0).
+// With S3S_ENGINE_DUP_AHEAD the head has ONE LDS wait behind the fresh table read instead of two (cpS and pass 1 of the next
+// window, lgkmcnt(0)); pass 2's read-back is issued there and waited for by the lgkmcnt(0) that opens .Lw_commit (or .Lw_x2) -
+// or by a ring path's lgkmcnt(0) in between, which then returns it early: every LDS wait is still lgkmcnt(0), and no vmcnt
+// changes (the next window's gather is issued at the same place in the order of the vector-memory accesses).  What may be in
+// the table when, and why the roll-back is safe against the commit and the ip-2 put: "ORDER ON THE TABLE" at the top of the file.
 #ifdef S3S_ENGINE_PW_DIRECT
 #error "S3S_ENGINE_SPEC needs the permuted stream load"
 #endif
@@ -570,6 +636,58 @@
   "s_andn2_b64 exec, s[74:75], s[84:85]\n\t"                                                               \
   "ds_write_b16 v149, %[cp]\n\t"                                                                           \
   "s_mov_b64 exec, -1\n\t"
+#ifdef S3S_ENGINE_DUP_AHEAD
+/* the next window's passes (all 64 lanes, exec = -1): pass 1 goes out behind the speculative table read ... */
+#define S3S_DUPA_PASS1                                                                                        \
+  "v_add_u32_e32 v117, 64, v148\n\t"                                                                       \
+  "ds_write_b16 v155, v117\n\t"                                                                            \
+  "ds_read_u16 v116, v155\n\t"
+/* ... pass 2 when it is back (s[84:85] = the lanes that lost pass 1); nobody waits for v115 before .Lw_commit / .Lw_x2 */
+#define S3S_DUPA_PASS2                                                                                        \
+  "s_mov_b64 exec, s[84:85]\n\t"                                                                           \
+  "ds_write_b16 v155, v117\n\t"                                                                            \
+  "s_mov_b64 exec, -1\n\t"                                                                                 \
+  "ds_read_u16 v115, v155\n\t"
+/* the roll-back: whoever holds a slot after pass 2 puts back what the head read in front of pass 1 (leaves exec = those lanes
+   = vcc; "ORDER ON THE TABLE" at the top of the file) */
+#define S3S_DUPA_ROLLBACK /* (after lgkmcnt(0)) */                                                            \
+  "v_cmpx_eq_u32_e32 vcc, v115, v117\n\t"                                                             \
+  "ds_write_b16 v155, v159\n\t"
+/* sequential entry: the records were built at the end of the previous window, and so was Dp (all lanes: .Lw_commit) */
+#define S3S_ENGINE_FIXED(NB, Y0, Y1, Y2, Y3, Z0, Z1, Z2, Z3, G, G0, G1, G2, G3, GN)                            \
+  ".Lw_winf" NB "_%=:\n\t"                                                                                 \
+  "s_sub_i32 s78, %[base], s76\n\t"                                                                        \
+  "v_cmp_le_u32_e64 s[74:75], s78, v129\n\t"                                                               \
+  "s_waitcnt lgkmcnt(0)\n\t" /* cp of this window, the permuted stream dwords of the next */               \
+  S3S_ENGINE_PW1_ALIGN(Z0, Z1, Z2, Z3)                                                                      \
+  "v_mul_lo_u32 v155, " Z1 ", s79\n\t"                                                                     \
+  "v_cmp_ne_u32_e64 vcc, %[cp], v159\n\t" /* stale lanes */                                                \
+  "v_lshrrev_b32_e32 v156, 19, v155\n\t"                                                                   \
+  "v_lshlrev_b32_e32 v155, 1, v156\n\t"                                                                    \
+  "ds_read_u16 v159, v155\n\t" /* cpS of the next window: the table before its passes and this window's commit */\
+  S3S_DUPA_PASS1                                                                                           \
+  "s_mov_b64 exec, s[74:75]\n\t"                                                                           \
+  "v_mov_b32_e32 v150, 0x80000000\n\t" /* (a literal next to vcc would be two constant-bus reads: not on gfx9) */ \
+  "v_cndmask_b32_e32 %[info], %[info], v150, vcc\n\t" /* (live lanes only: exec) */                        \
+  "v_cmp_ne_u32_e64 s[82:83], 0, %[info]\n\t" /* live lanes with a matching candidate, or stale */         \
+  "s_mov_b64 exec, -1\n\t"                                                                                 \
+  "s_and_b64 %[Dp], %[Dp], s[74:75]\n\t"                                                                   \
+  S3S_ENGINE_RUN_INIT                                                                                      \
+  "s_waitcnt lgkmcnt(0)\n\t" /* cpS and pass 1 of the next window */                                       \
+  "v_cmp_ne_u32_e64 s[84:85], v116, v117\n\t"                                                              \
+  /* (the compare's result reaches the scalar unit ~25 cycles later: the next window's gather goes out in between) */\
+  "v_add_u32_e32 v150, -4, v159\n\t"                                                                       \
+  "v_max_i32_e32 v150, 0, v150\n\t"                                                                        \
+  "global_load_dwordx4 " GN ", v150, %[inp]" S3S_ENGINE_GATHER_POL "\n\t"                                    \
+  "s_or_b64 %[ED], s[82:83], %[Dp]\n\t"                                                                    \
+  S3S_DUPA_PASS2
+#define S3S_DUPA_MISS /* (the window's own passes are rolled back: the next window's, with a wait of their own) */ \
+  S3S_DUPA_PASS1                                                                                           \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
+  "v_cmp_ne_u32_e64 s[84:85], v116, v117\n\t"                                                              \
+  S3S_DUPA_PASS2
+#else
+#define S3S_DUPA_MISS
 /* sequential entry: the records were built at the end of the previous window */
 #define S3S_ENGINE_FIXED(NB, Y0, Y1, Y2, Y3, Z0, Z1, Z2, Z3, G, G0, G1, G2, G3, GN)                            \
   ".Lw_winf" NB "_%=:\n\t"                                                                                 \
@@ -580,6 +698,7 @@
   S3S_SPEC_PASS2_AND_NEXT_GATHER(GN)                                                                       \
   S3S_SPEC_PASS2_DONE("")                                                                                  \
   "s_or_b64 %[ED], s[82:83], %[Dp]\n\t"
+#endif
 #define S3S_SPEC_MISS_BODY(Z0, Z1, Z2, Z3, G, GN)                                                              \
   S3S_SPEC_HEAD(Z0, Z1, Z2, Z3, "")                                                                        \
   "v_cmp_gt_u32_e32 vcc, 4, %[cp]\n\t" /* near0: kept in vcc until the event records are built */          \
@@ -588,7 +707,8 @@
   "global_load_dwordx4 " G ", v150, %[inp]" S3S_ENGINE_GATHER_POL "\n\t"                                     \
   "s_mov_b32 %[code], -1\n\t"                                                                              \
   S3S_SPEC_PASS2_AND_NEXT_GATHER(GN)                                                                       \
-  S3S_SPEC_PASS2_DONE("")
+  S3S_SPEC_PASS2_DONE("")                                                                                  \
+  S3S_DUPA_MISS
 /* any other entry (out of line): gather with the fresh candidates, as without speculation */
 #define S3S_ENGINE_FIXED_MISS(NB, X0, X1, X2, X3, Y0, Y1, Y2, Y3, Z0, Z1, Z2, Z3, G, G0, G1, G2, G3, GN)       \
   ".Lw_winm" NB "_%=:\n\t"                                                                                 \
@@ -639,13 +759,6 @@
   "s_mov_b32 %[code], -1\n\t"                                                                              \
   "s_waitcnt vmcnt(0)\n\t"                                                                                 \
   "s_branch .Lw_info" NB "_%=\n\t"                                                                         \
-  /* the first extension of this window was issued at the end of the previous one: only wait for it */     \
-  ".Lw_exth" NB "_%=:\n\t"                                                                                 \
-  "s_and_b32 s97, s87, 0xc00000\n\t"                                                                       \
-  S3S_RING_EXTH_MFULL(NB)                                                                                  \
-  S3S_RING_EXTHW(NB)                                                                                       \
-  "s_waitcnt vmcnt(2)\n\t"                                                                                 \
-  "s_branch .Lw_fwcmp" NB "_%=\n\t"                                                                        \
   S3S_ENGINE_NVW(NB)
 #define S3S_ENGINE_NEXT_TABLE_READ(Z1) /* (h was moved in the commit's shadow) */                            \
   "v_mov_b32_e32 v149, v155\n\t"                                                                           \
@@ -748,16 +861,36 @@
   "s_mov_b64 exec, -1\n\t"
 #define S3S_ENGINE_CFIX(NB)
 #define S3S_ENGINE_PERM_AT_END S3S_ENGINE_PW2_PERM
+#define S3S_DUPA_X2
 #else
 /* (round 5) the commit's store and its read-back go out FIRST; the next window's records and the extension prefetch are
    computed while that LDS round trip flies, and the compare's way to the scalar unit is covered by the stream permutes: the
    "did a lower position end up in a slot two kept lanes share" check used to be a round trip of its own in half the windows */
+#ifdef S3S_ENGINE_DUP_AHEAD
+/* the next window's passes are back: roll them back IN FRONT of the commit's store; Dp (dead in this window from here on: this
+   commit does not look at it) becomes the next window's, over all 64 lanes: lost pass 1, or does not hold the slot after pass 2 */
+#define S3S_DUPA_COMMIT_HEAD                                                                                  \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
+  "v_cmp_ne_u32_e64 s[82:83], v116, v117\n\t" /* (all lanes: in front of the roll-back's exec) */          \
+  S3S_DUPA_ROLLBACK
+#define S3S_DUPA_COMMIT_DP "s_orn2_b64 %[Dp], s[82:83], vcc\n\t"
+#define S3S_DUPA_X2                                                                                           \
+  "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
+  S3S_DUPA_ROLLBACK                                                                                        \
+  "s_mov_b64 exec, -1\n\t"
+#else
+#define S3S_DUPA_COMMIT_HEAD
+#define S3S_DUPA_COMMIT_DP
+#define S3S_DUPA_X2
+#endif
 #define S3S_ENGINE_COMMIT(NB, Z0, Z1, Z2, Z3, N0, N1, N2, N3)                                                   \
   ".Lw_commit" NB "_%=:\n\t"                                                                                \
+  S3S_DUPA_COMMIT_HEAD                                                                                     \
   "s_mov_b64 exec, %[K]\n\t"                                                                               \
   "ds_write_b16 v149, v148\n\t"                                                                            \
   "ds_read_u16 v128, v149\n\t"                                                                             \
   "s_mov_b64 exec, -1\n\t"                                                                                 \
+  S3S_DUPA_COMMIT_DP                                                                                       \
   S3S_ENGINE_SPEC_COMMIT(NB, Z0, Z1, Z2, Z3, N0, N1, N2, N3)                                                \
   "s_waitcnt lgkmcnt(0)\n\t"                                                                               \
   "s_mov_b64 exec, %[K]\n\t"                                                                               \
@@ -1059,6 +1192,111 @@
 #define S3S_ENGINE_PEND_FAR(NB) "s_branch .Lw_pendset" NB "_%=\n\t"
 #endif
 
+// ---- pieces of the run loop that S3S_ENGINE_LAYOUT places (same text in both orders) ----
+/* the extension's load addresses: v125 = ip + 4 + 4 * lane, v126 = the same on the source side, s98 = offset */
+#define S3S_ENGINE_EXT_ADDR                                                                                   \
+  "s_add_i32 s97, s89, 4\n\t"                                                                              \
+  "v_lshl_add_u32 v125, v129, 2, s97\n\t"                                                                  \
+  "s_sub_i32 s98, s89, s88\n\t"                                                                            \
+  "v_subrev_u32_e32 v126, s98, v125\n\t"
+#define S3S_ENGINE_EXT_LOADS                                                                                  \
+  "global_load_dword v130, v125, %[inp]\n\t"                                                               \
+  S3S_ENGINE_ABL_DUP_IPSIDE                                                                                \
+  "global_load_dword v131, v126, %[inp]\n\t"
+/* the extension issued on demand, up to the arrival of its forward data (.Lw_fwcmp follows) */
+#define S3S_ENGINE_EXT_ONDEMAND(NB)                                                                           \
+  S3S_ENGINE_EXT_ADDR                                                                                      \
+  S3S_RING_EXT(NB)                                                                                         \
+  S3S_ENGINE_EXT_LOADS                                                                                     \
+  "s_and_b32 s97, s87, 0xc00000\n\t"                                                                       \
+  "s_cbranch_scc1 .Lw_mfull" NB "_%=\n\t"                                                                  \
+  ".Lw_fwonly" NB "_%=:\n\t"                                                                               \
+  "s_waitcnt vmcnt(0)\n\t"
+/* the first extension of this window was issued at the end of the previous one: only wait for it (.Lw_fwcmp follows) */
+#define S3S_ENGINE_EXT_EARLY(NB)                                                                              \
+  ".Lw_exth" NB "_%=:\n\t"                                                                                 \
+  "s_and_b32 s97, s87, 0xc00000\n\t"                                                                       \
+  S3S_RING_EXTH_MFULL(NB)                                                                                  \
+  S3S_RING_EXTHW(NB)                                                                                       \
+  "s_waitcnt vmcnt(2)\n\t"
+#if !defined(S3S_ENGINE_SPEC)
+#define S3S_ENGINE_EXT_INLINE(NB) S3S_ENGINE_EXT_ONDEMAND(NB)
+#define S3S_ENGINE_EXT_OUTLINE(NB)
+#elif !defined(S3S_ENGINE_LAYOUT)
+#define S3S_ENGINE_EXT_INLINE(NB)                                                                             \
+  S3S_ENGINE_SPEC_EXT(NB)                                                                                  \
+  S3S_ENGINE_EXT_ONDEMAND(NB)
+#define S3S_ENGINE_EXT_OUTLINE(NB)                                                                            \
+  S3S_ENGINE_EXT_EARLY(NB)                                                                                 \
+  "s_branch .Lw_fwcmp" NB "_%=\n\t"
+#else
+/* .Lw_ext: is this the extension that is already in flight? (any other extension overwrites its registers) */
+#define S3S_ENGINE_EXT_INLINE(NB)                                                                             \
+  "s_cmp_eq_u32 s86, %[code]\n\t"                                                                          \
+  "s_mov_b32 %[code], -1\n\t"                                                                              \
+  "s_cbranch_scc0 .Lw_extd" NB "_%=\n\t"                                                                   \
+  S3S_ENGINE_EXT_EARLY(NB)
+#define S3S_ENGINE_EXT_OUTLINE(NB)                                                                            \
+  ".Lw_extd" NB "_%=:\n\t"                                                                                 \
+  S3S_ENGINE_EXT_ONDEMAND(NB)                                                                              \
+  "s_branch .Lw_fwcmp" NB "_%=\n\t"
+#endif
+/* the backward part from memory (64 bytes in front of ip and of the source), the wait for both parts, the compares */
+#define S3S_ENGINE_EXTB(NB)                                                                                   \
+  ".Lw_extb" NB "_%=:\n\t"                                                                                 \
+  "s_min_i32 s99, s92, s88\n\t"                                                                            \
+  "v_mov_b32_e32 v127, 0\n\t"                                                                              \
+  "v_mov_b32_e32 v128, 1\n\t"                                                                              \
+  "v_cmp_gt_i32_e64 s[82:83], s99, v129\n\t"                                                               \
+  "s_add_i32 s97, s89, -1\n\t"                                                                             \
+  "s_add_i32 s98, s88, -1\n\t"                                                                             \
+  "s_and_saveexec_b64 s[84:85], s[82:83]\n\t"                                                              \
+  "v_sub_u32_e32 v123, s97, v129\n\t"                                                                      \
+  "v_sub_u32_e32 v124, s98, v129\n\t"                                                                      \
+  "global_load_ubyte v127, v123, %[inp]\n\t"                                                               \
+  "global_load_ubyte v128, v124, %[inp]\n\t"                                                               \
+  "s_mov_b64 exec, s[84:85]\n\t"                                                                           \
+  "s_waitcnt vmcnt(0)\n\t"                                                                                 \
+  S3S_RING_EXTBC(NB)                                                                                       \
+  "v_cmp_ne_u32_e64 s[82:83], v130, v131\n\t"                                                              \
+  "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
+  "v_xor_b32_e32 v123, v130, v131\n\t"
+#if defined(S3S_LZ4_RING) && defined(S3S_ENGINE_LAYOUT)
+#define S3S_ENGINE_EXTB_INLINE(NB)
+#define S3S_ENGINE_EXTB_OUTLINE(NB)                                                                           \
+  S3S_RING_EXTFG(NB)                                                                                       \
+  S3S_ENGINE_EXT_LOADS                                                                                     \
+  S3S_ENGINE_EXTB(NB)                                                                                      \
+  "s_branch .Lw_extbc2" NB "_%=\n\t"
+#else
+#define S3S_ENGINE_EXTB_INLINE(NB)                                                                            \
+  S3S_ENGINE_EXT_LOADS                                                                                     \
+  S3S_ENGINE_EXTB(NB)
+#define S3S_ENGINE_EXTB_OUTLINE(NB)
+#endif
+/* ---- the match left the window: ip-2 is either one of its last two lanes or goes to the next window ---- */
+#define S3S_ENGINE_LEAVE(NB)                                                                                  \
+  ".Lw_leave" NB "_%=:\n\t"                                                                                \
+  "s_add_i32 s99, %[anchor], -2\n\t"                                                                       \
+  "s_lshl_b64 s[82:83], 1, s98\n\t"                                                                        \
+  "s_cmp_lt_i32 s98, 64\n\t"                                                                               \
+  "s_cselect_b64 s[82:83], s[82:83], 0\n\t"                                                                \
+  "s_cselect_b32 %[pendq], %[pendq], s99\n\t"                                                              \
+  "s_or_b64 %[K], %[K], s[82:83]\n\t"                                                                      \
+  "s_mov_b32 %[base], %[anchor]\n\t"                                                                       \
+  "s_mov_b32 %[t0], 0\n\t"
+#ifdef S3S_ENGINE_LAYOUT
+#define S3S_ENGINE_LEAVE_R6(NB)
+#define S3S_ENGINE_LEAVE_AT_COMMIT(NB)                                                                        \
+  "s_branch .Lw_commit" NB "_%=\n\t"                                                                       \
+  S3S_ENGINE_LEAVE(NB)
+#else
+#define S3S_ENGINE_LEAVE_R6(NB)                                                                               \
+  S3S_ENGINE_LEAVE(NB)                                                                                     \
+  "s_branch .Lw_commit" NB "_%=\n\t"
+#define S3S_ENGINE_LEAVE_AT_COMMIT(NB)
+#endif
+
 // One step of the rotation: the dispatch for register roles B (X = bytes of window pk, Y = the next window, Z = the
 // one after) followed by the window body for roles NB (pw0 = Y, pw1 = Z, pw2 = X), which the dispatch falls into
 // when the window to run directly follows window pk.  NNB: the roles after a skipped window.  TAIL closes the ring.
@@ -1088,19 +1326,7 @@
   "s_cbranch_scc0 .Lw_len" NB "_%=\n\t"                                                                    \
   /* cooperative extension, one round: 256 B forward; backward (64 B) only when the record's count is capped or unknown */\
   ".Lw_ext" NB "_%=:\n\t"                                                                                  \
-  S3S_ENGINE_SPEC_EXT(NB)                                                                                  \
-  "s_add_i32 s97, s89, 4\n\t"                                                                              \
-  "v_lshl_add_u32 v125, v129, 2, s97\n\t"                                                                  \
-  "s_sub_i32 s98, s89, s88\n\t"                                                                            \
-  "v_subrev_u32_e32 v126, s98, v125\n\t"                                                                   \
-  S3S_RING_EXT(NB)                                                                                         \
-  "global_load_dword v130, v125, %[inp]\n\t"                                                               \
-  S3S_ENGINE_ABL_DUP_IPSIDE                                                                                \
-  "global_load_dword v131, v126, %[inp]\n\t"                                                               \
-  "s_and_b32 s97, s87, 0xc00000\n\t"                                                                       \
-  "s_cbranch_scc1 .Lw_mfull" NB "_%=\n\t"                                                                  \
-  ".Lw_fwonly" NB "_%=:\n\t"                                                                               \
-  "s_waitcnt vmcnt(0)\n\t"                                                                                 \
+  S3S_ENGINE_EXT_INLINE(NB)                                                                                \
   S3S_ENGINE_SPEC_FWCMP(NB)                                                                                \
   "v_cmp_ne_u32_e64 s[82:83], v130, v131\n\t"                                                              \
   "v_xor_b32_e32 v123, v130, v131\n\t"                                                                     \
@@ -1130,17 +1356,7 @@
   "s_bitset1_b64 %[K], s98\n\t"                                                                            \
   "s_lshl_b64 s[80:81], -1, %[rs]\n\t"                                                                     \
   "s_branch .Lw_top" NB "_%=\n\t"                                                                          \
-  /* ---- the match left the window: ip-2 is either one of its last two lanes or goes to the next window ---- */\
-  ".Lw_leave" NB "_%=:\n\t"                                                                                \
-  "s_add_i32 s99, %[anchor], -2\n\t"                                                                       \
-  "s_lshl_b64 s[82:83], 1, s98\n\t"                                                                        \
-  "s_cmp_lt_i32 s98, 64\n\t"                                                                               \
-  "s_cselect_b64 s[82:83], s[82:83], 0\n\t"                                                                \
-  "s_cselect_b32 %[pendq], %[pendq], s99\n\t"                                                              \
-  "s_or_b64 %[K], %[K], s[82:83]\n\t"                                                                      \
-  "s_mov_b32 %[base], %[anchor]\n\t"                                                                       \
-  "s_mov_b32 %[t0], 0\n\t"                                                                                 \
-  "s_branch .Lw_commit" NB "_%=\n\t"                                                                       \
+  S3S_ENGINE_LEAVE_R6(NB)                                                                                  \
   /* ---- extension with the backward part ---- */                                                         \
   ".Lw_mfull" NB "_%=:\n\t"                                                                                \
   "s_bitcmp1_b32 s87, 23\n\t"                                                                              \
@@ -1150,32 +1366,9 @@
   "s_branch .Lw_extb" NB "_%=\n\t"                                                                         \
   ".Lw_extfull" NB "_%=:\n\t"                                                                              \
   S3S_ENGINE_SPEC_EXTFULL(NB)                                                                              \
-  "s_add_i32 s97, s89, 4\n\t"                                                                              \
-  "v_lshl_add_u32 v125, v129, 2, s97\n\t"                                                                  \
-  "s_sub_i32 s98, s89, s88\n\t"                                                                            \
-  "v_subrev_u32_e32 v126, s98, v125\n\t"                                                                   \
+  S3S_ENGINE_EXT_ADDR                                                                                      \
   S3S_RING_EXTFULL(NB)                                                                                     \
-  "global_load_dword v130, v125, %[inp]\n\t"                                                               \
-  S3S_ENGINE_ABL_DUP_IPSIDE                                                                                \
-  "global_load_dword v131, v126, %[inp]\n\t"                                                               \
-  ".Lw_extb" NB "_%=:\n\t"                                                                                 \
-  "s_min_i32 s99, s92, s88\n\t"                                                                            \
-  "v_mov_b32_e32 v127, 0\n\t"                                                                              \
-  "v_mov_b32_e32 v128, 1\n\t"                                                                              \
-  "v_cmp_gt_i32_e64 s[82:83], s99, v129\n\t"                                                               \
-  "s_add_i32 s97, s89, -1\n\t"                                                                             \
-  "s_add_i32 s98, s88, -1\n\t"                                                                             \
-  "s_and_saveexec_b64 s[84:85], s[82:83]\n\t"                                                              \
-  "v_sub_u32_e32 v123, s97, v129\n\t"                                                                      \
-  "v_sub_u32_e32 v124, s98, v129\n\t"                                                                      \
-  "global_load_ubyte v127, v123, %[inp]\n\t"                                                               \
-  "global_load_ubyte v128, v124, %[inp]\n\t"                                                               \
-  "s_mov_b64 exec, s[84:85]\n\t"                                                                           \
-  "s_waitcnt vmcnt(0)\n\t"                                                                                 \
-  S3S_RING_EXTBC(NB)                                                                                       \
-  "v_cmp_ne_u32_e64 s[82:83], v130, v131\n\t"                                                              \
-  "v_cmp_ne_u32_e64 s[84:85], v127, v128\n\t"                                                              \
-  "v_xor_b32_e32 v123, v130, v131\n\t"                                                                     \
+  S3S_ENGINE_EXTB_INLINE(NB)                                                                               \
   S3S_RING_EXTBC2(NB)                                                                                      \
   "s_ff1_i32_b64 s97, s[84:85]\n\t"                                                                        \
   "s_min_u32 s97, s97, 63\n\t"                                                                             \
@@ -1223,6 +1416,8 @@
   "s_andn2_b64 %[ED], %[ED], s[84:85]\n\t"                                                                 \
   "s_branch .Lw_top" NB "_%=\n\t"                                                                          \
   S3S_ENGINE_FIXED_MISS(NB, X0, X1, X2, X3, Y0, Y1, Y2, Y3, Z0, Z1, Z2, Z3, G, G0, G1, G2, G3, GN)               \
+  S3S_ENGINE_EXT_OUTLINE(NB)                                                                               \
+  S3S_ENGINE_EXTB_OUTLINE(NB)                                                                              \
   S3S_ENGINE_CFIX(NB)                                                                                      \
   S3S_ENGINE_FLUSH_STUB(NB)                                                                                \
   ".Lw_out0" NB "_%=:\n\t"                                                                                 \
@@ -1230,6 +1425,7 @@
   "s_branch .Lw_out" NB "_%=\n\t"                                                                          \
   ".Lw_x2" NB "_%=:\n\t"                                                                                    \
   S3S_ENGINE_SPEC_X2(NB)                                                                                   \
+  S3S_DUPA_X2                                                                                              \
   "s_cmp_lg_u64 %[K], 0\n\t"                                                                               \
   "s_cselect_b64 %[valid], -1, %[valid]\n\t"                                                               \
   "s_mov_b32 %[code], 2\n\t"                                                                               \
@@ -1294,6 +1490,7 @@
   "s_add_i32 s98, s98, s97\n\t"                                                                            \
   "s_sub_i32 %[t0], s98, %[rs]\n\t"                                                                        \
   /* (a run that leaves its consecutive part comes out with t0 = 66: the ring condition below hands it to the general batch) */\
+  S3S_ENGINE_LEAVE_AT_COMMIT(NB)                                                                           \
   /* ---- commit: the highest kept lane of every hash group writes ---- */                                    \
   S3S_ENGINE_COMMIT(NB, Z0, Z1, Z2, Z3, N0, N1, N2, N3)                                                    \
   /* ---- LZ4_putPosition(ip - 2) behind the window (its bytes are in the registers of the next two windows) ---- */\
