@@ -492,7 +492,8 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          answer to fall back, and the units of an encrypted range are new to a caller (below) - s3s_dstream_open_encrypted
  *          is the opt-in.  Both keep the one-shot call.  S3S_OPT_LZ4_DECODE_VARIANT = 3 WORKS: a feed launches whichever
  *          decoder the option names.
- * Not here a streaming map side, a reader in the C++ host mirror, a batched feed of several streams.
+ * Not here a reader in the C++ host mirror, a batched feed of several streams.  (The streaming map side is s3s_cstream_*,
+ *          below.)
  *
  * Under Spark IO encryption: s3s_dstream_open_encrypted (ABI 11, additive: callers detect support by the symbol) takes the
  * arguments of s3s_dstream_open and makes its checks, requires the layer to be on (off: S3S_E_INVALID) and refuses
@@ -590,6 +591,78 @@ int64_t s3s_dstream_position(const s3s_dstream* s);
 /* Frees the stream.  S3S_OK at the end of the range with every partition verified; the stream's error when it has one;
  * S3S_E_BAD_FRAME when the range was not read to its end (what a reader sees that closes a truncated stream). */
 int s3s_dstream_close(s3s_dstream* s);
+
+/* ---- map side, streaming: a map output compressed window by window, in bounded memory -------------------------------------
+ * (ABI 11, additive, no new option key: callers detect support by the symbols.)  Every s3s_compress_map_output* call needs the
+ * whole map output, the whole .data image and one slot per codec block resident at once.  The reference never holds a map
+ * output like that: shuffle/S3ShuffleMapOutputWriter.scala:43-49 puts a BufferedOutputStream of dispatcher.bufferSize in front
+ * of the object, :136-202 writes partition after partition through a codec stream and learns a partition's length as it
+ * closes.  LZ4Block frames, Snappy chunks and LZF chunks are independent blocks cut at multiples of the block size from the
+ * partition's start, and the per-partition checksums continue across calls: an s3s_cstream that takes only whole blocks
+ * writes the SAME BYTES as the one-shot call and keeps nothing on the device between feeds.
+ *
+ * Window   d_src[0, src_len) are the source bytes that start at s3s_cstream_position().  part_ends[0, n_ends) are host-side,
+ *          window-relative, ascending offsets 0 <= e <= src_len: a partition ends at each.  Equal neighbours are empty
+ *          partitions; an end at 0 in front of an open partition that has bytes closes that partition, with nothing consumed of
+ *          the open partition it is an empty partition.  Bytes behind the last end belong to the partition that stays open.
+ *          The caller presents again what was not consumed, with the ends rebased.  The stream does not know the number of
+ *          partitions in advance.
+ * Unit     (a) a block: blockSize source bytes of the open partition, or the partition's remaining bytes when its end lies in
+ *          the window.  The Snappy 16-byte stream header belongs to the unit of a partition's first block; a Snappy chunk above
+ *          one fragment is one unit, its head and all its fragments.  (b) the end of a non-empty LZ4 partition: the 21-byte
+ *          end frame, which consumes no source bytes.  For the other codecs the end has no bytes and is passed together with the
+ *          last block; the end of an empty partition is passed as soon as every unit in front of it is taken.  Bytes behind
+ *          the last end that do not make a whole block are not consumed.  For S3S_CODEC_NONE a unit is a byte.
+ * A feed   takes the longest prefix of units whose image bytes, as compressed, fit dst_capacity, writes them to dst[0, out_len)
+ *          and nothing at or beyond out_len.  For every end it passed it writes, in order, the partition's image length to
+ *          out_lengths and its checksum over the image bytes to out_checksums (may be NULL iff checksum NONE); both arrays
+ *          hold n_ends entries, [0, parts_closed) are valid.
+ * Progress the first unit does not fit and no end lies in front of it: S3S_E_CAPACITY, need_dst is its exact image size,
+ *          nothing is consumed, the stream stays usable.  The window shows no whole unit and no end: S3S_OK, consumed = 0,
+ *          need_src is the block size in force (LZF: 65 535; NONE: 1).  An empty window with no ends is S3S_OK.
+ * Result   with src_offsets built from the ends, on a context with the same options: the concatenation of all dst outputs is
+ *          byte for byte the .data image s3s_compress_map_output_device writes, the lengths are the differences of its index,
+ *          the checksums are its checksums - for every schedule of windows and capacities.  The output is a function of
+ *          source, ends and options, not of the feeds.
+ * Codecs   S3S_CODEC_NONE, LZ4, Snappy, and LZF when S3S_OPT_LZF_COMPRESS is 1, at every block size the one-shot call takes
+ *          through keys 1, 2 and 8 (the 32-bit-table LZ4 parse and the fragment-parallel Snappy chunks included).  The block
+ *          size and the LZ4 / Snappy variants are read at open and bound to the stream.  S3S_OPT_LZ4_VARIANT = 9 runs 11
+ *          without timing rounds, as a batched call does; S3S_OPT_LZ4_VARIANT_USED reports the parse run.
+ * Refused  at open with S3S_E_UNSUPPORTED, context intact: S3S_CODEC_ZSTD (the frame header this library writes carries the
+ *          8-byte content size of a partition whose end a stream has not seen); LZF with the option off; a context with IO
+ *          encryption on (the IV unit is a follow-up, as it was for s3s_dstream_open).  Encryption switched on after open
+ *          makes feeds answer S3S_E_UNSUPPORTED.  A feed answers S3S_E_INVALID, with nothing changed, for ends that are
+ *          negative, descending or beyond src_len, null pointers with non-zero lengths, negative sizes; a window with more
+ *          codec blocks than the one-shot call takes answers S3S_E_UNSUPPORTED.
+ * State    host-only: position, bytes written, source and image bytes of the open partition, its carried checksum.  No device
+ *          memory between feeds: a feed works in the context's workspace, and other calls on the same context may run between
+ *          two feeds.  s3s_cstream_feed (host buffers) stages src_len + dst_capacity bytes there.
+ * Speed    the stream buys bounded memory, not speed: a window below about 80 MiB does not fill the chip's 2 560 resident
+ *          wavefronts, and every feed pays one scan, one cut and one host wait (profiles/compress_stream.md has the figures).
+ * Close    frees the stream.  S3S_OK when no byte of the open partition has been consumed, else S3S_E_INVALID: the image ends
+ *          inside a codec stream.
+ * Not here Zstandard, IO encryption, the JNI natives and the Scala writer, a batched feed of several streams. */
+typedef struct s3s_cstream s3s_cstream;
+typedef struct s3s_cstream_result {
+  int64_t consumed;      /* source bytes of this window taken; the next window starts there */
+  int64_t out_len;       /* image bytes written to dst by this feed */
+  int64_t need_src;      /* S3S_OK with consumed == 0 and no end passed, because the window holds no whole unit: the window
+                            length that holds one; else 0 */
+  int64_t need_dst;      /* S3S_E_CAPACITY: exact image size of the first unit; else 0 */
+  int32_t parts_closed;  /* partition ends passed by this feed: out_lengths / out_checksums [0, parts_closed) are valid */
+  int32_t reserved;
+} s3s_cstream_result;
+int s3s_cstream_open(s3s_ctx* ctx, int codec, int checksum_algo, s3s_cstream** out);
+int s3s_cstream_feed_device(s3s_cstream* s, const uint8_t* d_src, int64_t src_len, const int64_t* part_ends, int32_t n_ends,
+                            uint8_t* d_dst, int64_t dst_capacity, int64_t* out_lengths, int64_t* out_checksums,
+                            s3s_cstream_result* r);
+int s3s_cstream_feed(s3s_cstream* s, const uint8_t* src, int64_t src_len, const int64_t* part_ends, int32_t n_ends, /* host buffers */
+                     uint8_t* dst, int64_t dst_capacity, int64_t* out_lengths, int64_t* out_checksums, s3s_cstream_result* r);
+/* a dst_capacity with which a feed of this shape never answers S3S_E_CAPACITY (and takes every unit of its window) */
+int64_t s3s_cstream_feed_bound(const s3s_cstream* s, int64_t src_len, int32_t n_ends);
+int64_t s3s_cstream_position(const s3s_cstream* s); /* source bytes consumed so far */
+int64_t s3s_cstream_written(const s3s_cstream* s);  /* image bytes produced so far = image offset of the next feed's dst */
+int s3s_cstream_close(s3s_cstream* s);
 
 /* Page-locked host staging memory for the host-buffer entry points (no reference counterpart:
  * it replaces the heap byte[] of storage/S3BufferedInputStreamAdaptor.scala:13-19 — one

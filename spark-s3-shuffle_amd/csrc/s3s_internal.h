@@ -307,6 +307,21 @@ void launch_frames_cut(int codec, const Frame* d_frames, const uint32_t* d_frame
 void launch_checksum_seed(int algo, const int64_t* d_offsets, int32_t n, const void* d_tables, const int64_t* d_seeds,
                           int64_t* d_out, hipStream_t st);
 
+// ---- streaming map side (compress_stream.hip: s3s_cstream_feed*) -----------------------------------------------------------
+//   The cut of a window's plan at the caller's output capacity, behind the scan of the item sizes (compress_stream_kernels.hip;
+//   the arithmetic is compress_stream_core.h).  d_marks: one s3s_cs::Mark per item; d_part_first[n_pieces + 1]: first item of
+//   every piece of a partition (the last piece is the partition the window leaves open); first_last: the last item of the
+//   first unit (-1: no unit); ends0: ends passed in front of the first unit; open_img: image bytes the open partition has
+//   already.  d_result[s3s_cs::kCutWords]; d_piece_off[n_pieces + 1]; d_lengths[n_pieces - 1].
+void launch_cstream_cut(const void* d_marks, const int64_t* d_item_off, int32_t n_items, const int32_t* d_part_first, int32_t n_pieces,
+                        int64_t dst_capacity, int32_t first_last, int32_t ends0, int64_t open_img, int64_t* d_result,
+                        int64_t* d_piece_off, int64_t* d_lengths, hipStream_t st);
+//   launch_gather_items for the items [0, d_cut[0]) - the cut is read on the device, the grid covers all n_items
+void launch_gather_items_cut(const uint8_t* d_src, const Item* d_items, int32_t n_items, const int64_t* d_cut,
+                             const uint8_t* d_slots, int64_t slot_stride, const uint32_t* d_item_size,
+                             const int64_t* d_item_off, uint8_t* d_dst, int64_t dst_capacity,
+                             int32_t* d_status, hipStream_t st);
+
 // ---- device helpers shared by several kernels --------------------------------------------
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) {
   return __builtin_amdgcn_alignbit(x, x, 32 - r);

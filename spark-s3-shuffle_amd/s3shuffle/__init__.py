@@ -18,6 +18,8 @@ from .codec import (  # noqa: F401
     CODEC_ZSTD,
     Codec,
     CodecError,
+    CompressStream,
+    CompressStreamResult,
     DecodeStream,
     PinnedBuffer,
     device_count,

@@ -88,6 +88,12 @@ class StreamResult(ctypes.Structure):
                 ("need_dst", ctypes.c_int64), ("bad_partition", ctypes.c_int32), ("at_end", ctypes.c_int32)]
 
 
+class CompressStreamResult(ctypes.Structure):
+    """s3s_cstream_result (include/s3shuffle_codec.h): what one feed of a CompressStream did."""
+    _fields_ = [("consumed", ctypes.c_int64), ("out_len", ctypes.c_int64), ("need_src", ctypes.c_int64),
+                ("need_dst", ctypes.c_int64), ("parts_closed", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 def load_library() -> ctypes.CDLL:
     """Loads the HIP codec library.  Fails loudly if it has not been built."""
     global _LIB
@@ -172,6 +178,19 @@ def load_library() -> ctypes.CDLL:
         lib.s3s_dstream_open_encrypted.argtypes = lib.s3s_dstream_open.argtypes
     if hasattr(lib, "s3s_dstream_open_zstd"):  # resumable Zstandard streams (additive, detected by the symbol)
         lib.s3s_dstream_open_zstd.argtypes = [vp, ctypes.c_int, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]
+    if hasattr(lib, "s3s_cstream_open"):  # streaming map side (additive, detected by the symbols)
+        lib.s3s_cstream_open.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+        cfeed_args = [vp, vp, ctypes.c_int64, c_i64p, ctypes.c_int32, vp, ctypes.c_int64, c_i64p, c_i64p,
+                      ctypes.POINTER(CompressStreamResult)]
+        lib.s3s_cstream_feed.argtypes = cfeed_args
+        lib.s3s_cstream_feed_device.argtypes = cfeed_args
+        lib.s3s_cstream_feed_bound.restype = ctypes.c_int64
+        lib.s3s_cstream_feed_bound.argtypes = [vp, ctypes.c_int64, ctypes.c_int32]
+        lib.s3s_cstream_position.restype = ctypes.c_int64
+        lib.s3s_cstream_position.argtypes = [vp]
+        lib.s3s_cstream_written.restype = ctypes.c_int64
+        lib.s3s_cstream_written.argtypes = [vp]
+        lib.s3s_cstream_close.argtypes = [vp]
     if hasattr(lib, "s3s_dstream_held_bytes"):  # debug accessor: device bytes a stream (or, with NULL, all streams) holds between feeds
         lib.s3s_dstream_held_bytes.restype = ctypes.c_int64
         lib.s3s_dstream_held_bytes.argtypes = [vp]
@@ -411,6 +430,11 @@ class Codec:
                                                                 _p64(sd) if sd is not None else None, _p64(out)))
         return out[:n]
 
+    def compress_stream(self, codec: int, checksum: int) -> "CompressStream":
+        """A map output compressed window by window in bounded memory (s3s_cstream_*): the same bytes, lengths and checksums
+        as compress_map_output_device for the same source, ends and options."""
+        return CompressStream(self, codec, checksum)
+
     # ---- reduce side ---------------------------------------------------------------------------
     def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False,
                       window_log_max: Optional[int] = None) -> "DecodeStream":
@@ -583,6 +607,103 @@ class DecodeStream:
         self._s = None
         if check and rc != 0:
             raise CodecError(rc, "the stream was closed before the end of the range" if rc == E_BAD_FRAME else "the stream had failed")
+        return rc
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *exc):
+        self.close(check=exc_type is None)
+
+    def __del__(self):
+        try:
+            if self._s and getattr(self._ctx, "_h", None):
+                self.close(check=False)
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class CompressStream:
+    """One s3s_cstream: the streaming map side.  `feed` / `feed_device` take the window of source bytes that starts at
+    `position` and the window-relative offsets at which partitions end in it, and return the CompressStreamResult of the feed
+    with `.lengths` / `.checksums` (the image length and checksum of every partition the feed closed, `parts_closed` of them;
+    `.checksums` is None with CHECKSUM_NONE): `consumed` source bytes became `out_len` image bytes.  `consumed == 0` with
+    `need_src` asks for a longer window.  S3S_E_CAPACITY is NOT raised (the stream stays usable): the result carries
+    `need_dst` and `.code == E_CAPACITY`.  Every other error raises CodecError.  `last_result` is the result of the latest feed.
+    `close()` raises E_INVALID when bytes of the open partition have been consumed (the image would end inside a codec
+    stream).  Also a context manager (which closes quietly after an exception, loudly otherwise)."""
+
+    def __init__(self, codec_ctx: Codec, codec: int, checksum: int):
+        self._ctx = codec_ctx
+        self._lib = codec_ctx._lib
+        self._s = None
+        self._checksum = checksum
+        self.last_result = None
+        if not hasattr(self._lib, "s3s_cstream_open"):
+            raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_cstream_open")
+        h = ctypes.c_void_p(None)
+        codec_ctx._check(self._lib.s3s_cstream_open(codec_ctx._h, codec, checksum, ctypes.byref(h)))
+        self._s = h.value
+
+    @property
+    def position(self) -> int:
+        """Source bytes consumed so far."""
+        return int(self._lib.s3s_cstream_position(self._s))
+
+    @property
+    def written(self) -> int:
+        """Image bytes produced so far: the image offset of the next feed's output."""
+        return int(self._lib.s3s_cstream_written(self._s))
+
+    def feed_bound(self, src_len: int, n_ends: int) -> int:
+        """A dst capacity with which a feed of this shape never answers E_CAPACITY."""
+        r = int(self._lib.s3s_cstream_feed_bound(self._s, int(src_len), int(n_ends)))
+        if r < 0:
+            raise CodecError(r, "s3s_cstream_feed_bound")
+        return r
+
+    def _feed(self, fn, src_ptr, src_len, part_ends, dst_ptr, dst_capacity):
+        if not self._s:
+            raise ValueError("the stream is closed")
+        ends = _i64(part_ends)
+        n = len(ends)
+        lengths = np.zeros(max(n, 1), dtype=np.int64)
+        sums = np.zeros(max(n, 1), dtype=np.int64) if self._checksum != CHECKSUM_NONE else None
+        r = CompressStreamResult()
+        rc = fn(self._s, src_ptr, int(src_len), _p64(ends) if n else None, n, dst_ptr, int(dst_capacity),
+                _p64(lengths) if n else None, _p64(sums) if (n and sums is not None) else None, ctypes.byref(r))
+        r.code = int(rc)
+        r.lengths = lengths[: r.parts_closed]
+        r.checksums = sums[: r.parts_closed] if sums is not None else None
+        self.last_result = r
+        if rc != 0 and rc != E_CAPACITY:
+            self._ctx._check(rc)
+        return r
+
+    def feed(self, src: np.ndarray, part_ends, dst: np.ndarray, dst_capacity: Optional[int] = None) -> CompressStreamResult:
+        """Host buffers: `src` is the window (uint8), the image bytes land in dst[:result.out_len]."""
+        if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable):
+            raise ValueError("dst must be a writable C-contiguous uint8 array (the library writes into it)")
+        cap = dst.size if dst_capacity is None else int(dst_capacity)
+        if not 0 <= cap <= dst.size:
+            raise ValueError(f"dst_capacity {cap} is outside dst's {dst.size} bytes")
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        return self._feed(self._lib.s3s_cstream_feed, src.ctypes.data if src.size else None, src.size, part_ends,
+                          dst.ctypes.data if cap else None, cap)
+
+    def feed_device(self, d_src: int, src_len: int, part_ends, d_dst: int, dst_capacity: int) -> CompressStreamResult:
+        """Device pointers on the context's device."""
+        return self._feed(self._lib.s3s_cstream_feed_device, ctypes.c_void_p(d_src) if src_len else None, src_len, part_ends,
+                          ctypes.c_void_p(d_dst) if dst_capacity else None, dst_capacity)
+
+    def close(self, check: bool = True) -> int:
+        """Frees the stream; returns the code s3s_cstream_close gave (raises it when `check` and it is not S3S_OK)."""
+        if not self._s:
+            return 0
+        rc = int(self._lib.s3s_cstream_close(self._s))
+        self._s = None
+        if check and rc != 0:
+            raise CodecError(rc, "the stream was closed inside a partition: the image ends inside a codec stream")
         return rc
 
     def __enter__(self):
