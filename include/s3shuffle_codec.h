@@ -629,9 +629,11 @@ int s3s_dstream_close(s3s_dstream* s);
  *          size and the LZ4 / Snappy variants are read at open and bound to the stream.  S3S_OPT_LZ4_VARIANT = 9 runs 11
  *          without timing rounds, as a batched call does; S3S_OPT_LZ4_VARIANT_USED reports the parse run.
  * Refused  at open with S3S_E_UNSUPPORTED, context intact: S3S_CODEC_ZSTD (the frame header this library writes carries the
- *          8-byte content size of a partition whose end a stream has not seen); LZF with the option off; a context with IO
- *          encryption on (the IV unit is a follow-up, as it was for s3s_dstream_open).  Encryption switched on after open
- *          makes feeds answer S3S_E_UNSUPPORTED.  A feed answers S3S_E_INVALID, with nothing changed, for ends that are
+ *          8-byte content size of a partition whose end a stream has not seen); LZF with the option off; by
+ *          s3s_cstream_open, any context with IO encryption on: callers from before s3s_cstream_open_encrypted rely on that
+ *          answer to fall back, and the IV unit and the IVs of every feed are new to a caller (below) -
+ *          s3s_cstream_open_encrypted is the opt-in.  Encryption switched on after s3s_cstream_open makes that stream's
+ *          feeds answer S3S_E_UNSUPPORTED.  A feed answers S3S_E_INVALID, with nothing changed, for ends that are
  *          negative, descending or beyond src_len, null pointers with non-zero lengths, negative sizes; a window with more
  *          codec blocks than the one-shot call takes answers S3S_E_UNSUPPORTED.
  * State    host-only: position, bytes written, source and image bytes of the open partition, its carried checksum.  No device
@@ -641,7 +643,33 @@ int s3s_dstream_close(s3s_dstream* s);
  *          wavefronts, and every feed pays one scan, one cut and one host wait (profiles/compress_stream.md has the figures).
  * Close    frees the stream.  S3S_OK when no byte of the open partition has been consumed, else S3S_E_INVALID: the image ends
  *          inside a codec stream.
- * Not here Zstandard, IO encryption, the JNI natives and the Scala writer, a batched feed of several streams. */
+ * Not here Zstandard, the JNI natives and the Scala writer, a batched feed of several streams.
+ *
+ * Under Spark IO encryption: s3s_cstream_open_encrypted (ABI 11, additive: callers detect support by the symbol) takes the
+ * arguments of s3s_cstream_open and makes its checks, requires the layer to be on (off: S3S_E_INVALID) and refuses
+ * S3S_CODEC_ZSTD, and LZF with the option off, alike.  feed, feed_device, feed_bound, position, written and close work on
+ * the stream unchanged.  CTR is seekable - key stream block j is AES_K(IV + j) - so a feed continues the open partition's
+ * cipher text at any residue of a block.  The contract above holds with these changes only:
+ * IV       the 16-byte IV of a non-empty partition belongs to the unit of the partition's first block, as the Snappy stream
+ *          header does (Snappy: IV, stream header, chunk).  For S3S_CODEC_NONE the unit of a partition's first byte is 17
+ *          image bytes.  An empty partition stays 0 bytes.  need_dst, the capacity cut, the lengths, written and the checksums
+ *          count STORED bytes: IV plus cipher text, as in the one-shot call.  need_dst under S3S_CODEC_NONE is 17 at a
+ *          partition's first byte, else 1.  s3s_cstream_feed_bound adds 16 * (n_ends + 1).
+ * IVs      before EVERY feed the caller calls s3s_set_stream_ivs(ctx, ivs, n_ends + 1): a feed is a compress call, its
+ *          partitions are its n_ends + 1 pieces, entry j is the IV of the partition piece j belongs to.  An entry is used only
+ *          by the feed that takes that partition's first block; from then on the stream keeps that IV in its host state, and
+ *          entry 0 is ignored while the open partition already has image bytes.  A count other than n_ends + 1 (or no IVs set)
+ *          is S3S_E_INVALID before anything is launched, with the stream unchanged.  The array is consumed either way, also by
+ *          a feed that launches nothing.  A caller that presents the same IV every time it presents a partition's start gets
+ *          an image that is a function of source, ends, options, key and per-partition IVs, and not of the feeds.
+ * Key      the stream is bound to the key setting it was opened under, exactly as an encrypted s3s_dstream is: after any later
+ *          successful s3s_set_io_encryption on the context, on or off, the same key or another, its feeds answer S3S_E_INVALID
+ *          and it can only be closed.  No key material goes into the stream or into device memory.
+ * State    still host-only: it additionally holds the open partition's IV (16 bytes, wiped when the partition closes and at
+ *          close).  There is no device memory between feeds; one-shot calls on the context may run between two feeds.
+ * Result   the concatenation of all dst outputs is byte for byte what s3s_compress_map_output_device writes on a context with
+ *          the same options, key and IVs; the lengths are the differences of that call's index, the checksums its checksums.
+ * Not here Zstandard, the JNI natives and the Scala writer, a batched feed. */
 typedef struct s3s_cstream s3s_cstream;
 typedef struct s3s_cstream_result {
   int64_t consumed;      /* source bytes of this window taken; the next window starts there */
@@ -653,6 +681,7 @@ typedef struct s3s_cstream_result {
   int32_t reserved;
 } s3s_cstream_result;
 int s3s_cstream_open(s3s_ctx* ctx, int codec, int checksum_algo, s3s_cstream** out);
+int s3s_cstream_open_encrypted(s3s_ctx* ctx, int codec, int checksum_algo, s3s_cstream** out); /* under IO encryption (above) */
 int s3s_cstream_feed_device(s3s_cstream* s, const uint8_t* d_src, int64_t src_len, const int64_t* part_ends, int32_t n_ends,
                             uint8_t* d_dst, int64_t dst_capacity, int64_t* out_lengths, int64_t* out_checksums,
                             s3s_cstream_result* r);

@@ -9,6 +9,10 @@
 //   an LZ4 end    the 21-byte end frame of a non-empty partition; no source bytes
 // An end that has no bytes of its own (every codec but LZ4; an empty partition) is passed as soon as every unit in front of
 // it is taken.  S3S_CODEC_NONE has bytes for units and is cut without a plan (none_cut).
+// Under IO encryption (s3s_cstream_open_encrypted; tests/model/cstream_encrypted_model.cpp against
+// tests/cstream_units_encrypted.py) the 16-byte IV of a non-empty partition belongs to the unit of its first block: one more
+// plan record in front of that unit (iv_records), 17 image bytes for a partition's first byte under S3S_CODEC_NONE
+// (none_cut_encrypted), 16 more bytes a piece in feed_bound_encrypted.
 #pragma once
 #include <stdint.h>
 
@@ -122,6 +126,44 @@ inline Cut none_cut(int64_t src_len, const int64_t* ends, int32_t n_ends, int64_
   return c;
 }
 
+// S3S_CODEC_NONE under IO encryption (s3s_cstream_open_encrypted): the units are still bytes, but the unit of a partition's
+// first byte is 17 image bytes - its IV goes in front.  open_img > 0: the open partition's IV was written by an earlier feed.
+// piece_off[0, n_ends + 1] (or null) gets the stored piece offsets of the output, clamped to out_len (the E of the AES-CTR pass).
+inline Cut none_cut_encrypted(int64_t open_img, int64_t src_len, const int64_t* ends, int32_t n_ends, int64_t cap, int64_t* piece_off) {
+  Cut c;
+  int64_t start = 0, out = 0, first_need = 0;
+  bool open = true;  // every unit in front is taken
+  for (int32_t j = 0; j <= n_ends; j++) {
+    const int64_t end = j < n_ends ? ends[j] : src_len;
+    const int64_t len = end - start, lead = len > 0 && !(j == 0 && open_img > 0) ? 16 : 0;
+    if (piece_off) piece_off[j] = out;
+    if (open && lead + len <= cap - out) {
+      out += lead + len;
+      c.consumed = end;
+      if (j < n_ends) c.parts_closed = j + 1;
+    } else if (open) {
+      if (cap - out > lead) {  // the IV and at least one byte
+        c.consumed = start + (cap - out - lead);
+        out = cap;
+      } else if (out == 0 && c.parts_closed == 0) {
+        first_need = lead + 1;
+      }
+      open = false;
+    }
+    start = end;
+  }
+  if (piece_off) piece_off[n_ends + 1] = out;
+  if (first_need) {
+    c = Cut();
+    c.need_dst = first_need;
+    return c;
+  }
+  c.k = c.consumed;
+  c.out_len = out;
+  if (src_len == 0 && n_ends == 0) c.need_src = 1;
+  return c;
+}
+
 // piece_off[0, n_ends + 1]: where the pieces of partitions start in this feed's output (clamped to out_len); piece j < n_ends
 // is the partition that ends at ends[j].  The image lengths of the partitions the feed closes (the cut kernel writes the same):
 inline void closed_lengths(const State& s, const Cut& c, const int64_t* piece_off, int64_t* lengths) {
@@ -150,6 +192,11 @@ inline int64_t feed_bound(int codec, int64_t bs, int64_t src_len, int32_t n_ends
   return src_len + 7 * blocks;  // LZF
 }
 
+// ... under IO encryption: every piece may start its partition, with a 16-byte IV
+inline int64_t feed_bound_encrypted(int codec, int64_t bs, int64_t src_len, int32_t n_ends) {
+  return feed_bound(codec, bs, src_len, n_ends) + 16 * ((int64_t)n_ends + 1);
+}
+
 // ---- the cut kernel's side ---------------------------------------------------------------------------------------------------
 // One record per plan item (a unit is one or more items: a Snappy header, a chunk head and its fragments).
 struct Mark {
@@ -157,6 +204,18 @@ struct Mark {
   int32_t last;        // 1: the last item of its unit
   int32_t ends_after;  // ends passed once this item's unit is taken and the next is not
 };
+
+// IO encryption: one IV record (kItemIv, 16 image bytes) goes in front of the items of every unit that starts its partition.
+// Like a Snappy stream header it is not the last item of its unit, so the cut takes or leaves it with the block behind it.
+inline int32_t iv_records(const Unit& u, bool encrypted) { return encrypted && u.first ? 1 : 0; }
+
+// the marks of one unit's items [i0, i1); ends_after is corrected when the next unit arrives (mark_ends_after)
+inline void mark_unit(Mark* marks, int32_t i0, int32_t i1, const Unit& u, int32_t n_ends) {
+  for (int32_t i = i0; i < i1; i++) marks[i] = Mark{u.src_off + u.len, i == i1 - 1, n_ends};
+}
+inline void mark_ends_after(Mark* marks, int32_t i0, int32_t i1, int32_t ends_before) {
+  for (int32_t i = i0; i < i1; i++) marks[i].ends_after = ends_before;
+}
 
 // result words of the cut kernel
 enum { kCutK = 0, kCutConsumed = 1, kCutOutLen = 2, kCutNeedDst = 3, kCutPartsClosed = 4, kCutWords = 8 };

@@ -138,6 +138,16 @@ struct AesWindowIv {
 void launch_aes_ctr_window(const AesKeys& keys, int rounds, const AesWindowIv& iv0, const uint8_t* d_in, uint8_t* d_out,
                            const int64_t* d_stored_off, const int64_t* d_plain_off, uint8_t* d_iv_out, int32_t n_pieces, int64_t front,
                            int64_t window_len, hipStream_t st);
+// The map-side stream's form (aes_ctr_cstream.hip; the same arithmetic): the output d_dst[0, out_len) of one feed -> IV | cipher
+// text.  d_piece_off[n_pieces + 1] are the stored piece offsets of the output ([0] = 0, [n_pieces] = out_len, pieces behind the
+// cut empty), d_ivs one IV per piece (entry 0: the open partition's carried IV when `front` > 0 stored bytes of it lie in front
+// of the output).  out_bound: what the host knows out_len not to exceed (sizes the grid).
+//   kCsInPlace    d_dst holds a 16-byte hole + the plain bytes of every partition that starts in it; out_len is d_cut[kCutOutLen]
+//   kCsFromPlain  plain piece p at d_src + d_plain_off[p] (piece 0: its bytes behind the front)  ->  d_dst; out_len = out_bound
+enum { kCsInPlace = 0, kCsFromPlain = 1 };
+void launch_aes_ctr_cstream(int mode, const AesKeys& keys, int rounds, const uint8_t* d_src, uint8_t* d_dst, const int64_t* d_piece_off,
+                            const int64_t* d_plain_off, const uint8_t* d_ivs, const int64_t* d_cut, int32_t n_pieces, int64_t front,
+                            int64_t out_bound, hipStream_t st);
 // item_size = 16 for every kItemIv record (between the codec kernels and the scan)
 void launch_seed_iv_items(const Item* d_items, int32_t n_items, uint32_t* d_item_size, hipStream_t st);
 // exclusive scan of item sizes + partition index extraction

@@ -191,6 +191,8 @@ def load_library() -> ctypes.CDLL:
         lib.s3s_cstream_written.restype = ctypes.c_int64
         lib.s3s_cstream_written.argtypes = [vp]
         lib.s3s_cstream_close.argtypes = [vp]
+    if hasattr(lib, "s3s_cstream_open_encrypted"):  # the streaming map side under IO encryption (additive, detected by the symbol)
+        lib.s3s_cstream_open_encrypted.argtypes = lib.s3s_cstream_open.argtypes
     if hasattr(lib, "s3s_dstream_held_bytes"):  # debug accessor: device bytes a stream (or, with NULL, all streams) holds between feeds
         lib.s3s_dstream_held_bytes.restype = ctypes.c_int64
         lib.s3s_dstream_held_bytes.argtypes = [vp]
@@ -430,10 +432,12 @@ class Codec:
                                                                 _p64(sd) if sd is not None else None, _p64(out)))
         return out[:n]
 
-    def compress_stream(self, codec: int, checksum: int) -> "CompressStream":
+    def compress_stream(self, codec: int, checksum: int, encrypted: bool = False) -> "CompressStream":
         """A map output compressed window by window in bounded memory (s3s_cstream_*): the same bytes, lengths and checksums
-        as compress_map_output_device for the same source, ends and options."""
-        return CompressStream(self, codec, checksum)
+        as compress_map_output_device for the same source, ends and options.  `encrypted`: under IO encryption, through
+        s3s_cstream_open_encrypted (capacities, lengths and `written` count the stored bytes, IVs included; set_stream_ivs
+        with `len(part_ends) + 1` IVs goes in front of every feed)."""
+        return CompressStream(self, codec, checksum, encrypted=encrypted)
 
     # ---- reduce side ---------------------------------------------------------------------------
     def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False,
@@ -631,9 +635,13 @@ class CompressStream:
     `need_src` asks for a longer window.  S3S_E_CAPACITY is NOT raised (the stream stays usable): the result carries
     `need_dst` and `.code == E_CAPACITY`.  Every other error raises CodecError.  `last_result` is the result of the latest feed.
     `close()` raises E_INVALID when bytes of the open partition have been consumed (the image would end inside a codec
-    stream).  Also a context manager (which closes quietly after an exception, loudly otherwise)."""
+    stream).  Also a context manager (which closes quietly after an exception, loudly otherwise).
 
-    def __init__(self, codec_ctx: Codec, codec: int, checksum: int):
+    `encrypted=True` opens the stream with s3s_cstream_open_encrypted (the context's IO encryption must be on): a non-empty
+    partition is stored as its IV and the cipher text, the IV in the unit of the partition's first block.  Before EVERY feed
+    the caller gives `len(part_ends) + 1` IVs to Codec.set_stream_ivs: entry j is the IV of the partition piece j belongs to."""
+
+    def __init__(self, codec_ctx: Codec, codec: int, checksum: int, encrypted: bool = False):
         self._ctx = codec_ctx
         self._lib = codec_ctx._lib
         self._s = None
@@ -641,8 +649,11 @@ class CompressStream:
         self.last_result = None
         if not hasattr(self._lib, "s3s_cstream_open"):
             raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_cstream_open")
+        if encrypted and not hasattr(self._lib, "s3s_cstream_open_encrypted"):
+            raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_cstream_open_encrypted")
         h = ctypes.c_void_p(None)
-        codec_ctx._check(self._lib.s3s_cstream_open(codec_ctx._h, codec, checksum, ctypes.byref(h)))
+        fn = self._lib.s3s_cstream_open_encrypted if encrypted else self._lib.s3s_cstream_open
+        codec_ctx._check(fn(codec_ctx._h, codec, checksum, ctypes.byref(h)))
         self._s = h.value
 
     @property
