@@ -492,8 +492,8 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          answer to fall back, and the units of an encrypted range are new to a caller (below) - s3s_dstream_open_encrypted
  *          is the opt-in.  Both keep the one-shot call.  S3S_OPT_LZ4_DECODE_VARIANT = 3 WORKS: a feed launches whichever
  *          decoder the option names.
- * Not here a reader in the C++ host mirror, a batched feed of several streams.  (The streaming map side is s3s_cstream_*,
- *          below.)
+ * Not here a reader in the C++ host mirror.  (The batched feed of several streams is s3s_dstream_feed_batch*, behind the
+ *          streaming map side; the streaming map side is s3s_cstream_*, below.)
  *
  * Under Spark IO encryption: s3s_dstream_open_encrypted (ABI 11, additive: callers detect support by the symbol) takes the
  * arguments of s3s_dstream_open and makes its checks, requires the layer to be on (off: S3S_E_INVALID) and refuses
@@ -560,7 +560,8 @@ int s3s_checksum_ranges_seeded_device(s3s_ctx* ctx, int checksum_algo, const uin
  *          usable.  During a feed the workspace additionally holds the open frame's history plus what it decodes in the feed.
  * Result   the concatenation of all dst outputs is what s3s_decompress_range_device writes for the same range, whatever
  *          S3S_OPT_ZSTD_DECODE_VARIANT and S3S_OPT_ZSTD_DECODE_STAGED are set to.
- * Not here frames with a content checksum, Zstandard under IO encryption, a batched feed. */
+ * Not here frames with a content checksum, Zstandard under IO encryption.  In a batched feed (s3s_dstream_feed_batch*, below)
+ *          a Zstandard stream is fed on its own inside the call. */
 typedef struct s3s_dstream s3s_dstream;
 typedef struct s3s_dstream_result {
   int64_t consumed;      /* bytes of this window taken; the next window starts there */
@@ -692,6 +693,52 @@ int64_t s3s_cstream_feed_bound(const s3s_cstream* s, int64_t src_len, int32_t n_
 int64_t s3s_cstream_position(const s3s_cstream* s); /* source bytes consumed so far */
 int64_t s3s_cstream_written(const s3s_cstream* s);  /* image bytes produced so far = image offset of the next feed's dst */
 int s3s_cstream_close(s3s_cstream* s);
+
+/* ---- reduce side, streaming: the batched feed (ABI 11, additive: callers detect support by the symbol; no option key) ------
+ * The reference's reduce task never reads one stream at a time: S3BufferedPrefetchIterator keeps up to
+ * spark.shuffle.s3.maxConcurrencyTask (10) fetches open, each behind a buffer of spark.shuffle.s3.bufferSize (8 MiB), together
+ * under spark.shuffle.s3.maxBufferSizeTask (128 MiB) - S3ShuffleDispatcher.scala:55-57.  A feed has a floor of about half a
+ * millisecond whatever it holds (three host waits and the serial chains of discovery); s3s_dstream_feed_batch_device takes ONE
+ * WINDOW OF EACH OF SEVERAL STREAMS and pays that floor once per call.
+ *
+ * Contract every entry gets what s3s_dstream_feed_device(stream, d_comp, comp_len, d_dst, dst_capacity, &result) would have
+ *          produced for that stream alone: status and every field of result, the bytes d_dst[0, out_len) with nothing written
+ *          at or beyond d_dst + dst_capacity, and the stream's state afterwards - position, carried checksum, sticky error.
+ *          One entry's failure does not touch another entry: a sticky error from an earlier feed, S3S_E_CAPACITY with need_dst,
+ *          a refused Snappy claim, a wrong checksum and a corrupt frame are that entry's alone.
+ * Returns  S3S_OK, or the status of the first entry, in order, that is not S3S_OK (the rule of
+ *          s3s_decompress_ranges_batch_device).  Entries are stamped S3S_STATUS_NOT_RUN on entry to the call.
+ * Refused  before anything is launched, with S3S_E_INVALID and every stream unchanged: a null ctx, a negative n, null entries
+ *          with n > 0, a null stream, a stream opened on another context, the same stream twice, streams that differ in codec
+ *          or checksum algorithm.  n == 0 is S3S_OK.
+ * Caller   promises that the windows and the destinations of different entries do not overlap each other; the library does
+ *          not check it.
+ * Batched  plain LZ4, Snappy and LZF streams: three host waits per call whatever n is (checksums + discovery; frame tables +
+ *          the cut of every window at its own dst_capacity; one decode launch over the frames of all windows), and no stream's
+ *          state is committed before the decode's verdict is known.  When that verdict is bad - a corrupt payload, or an LZ4
+ *          frame above 32 MiB that needs the ring decoder - the undecided entries are fed one by one through the single feed,
+ *          which says whose it was.  S3S_OPT_LZ4_DECODE_VARIANT is honoured.
+ * One by one, in order, through the single feed inside the call (the contract holds for every stream the library can open):
+ *          n == 1, S3S_CODEC_NONE, any stream of s3s_dstream_open_encrypted or s3s_dstream_open_zstd, a context with IO
+ *          encryption on.
+ * Memory   the device form works in the context's workspace.  s3s_dstream_feed_batch (HOST addresses in d_comp / d_dst) stages
+ *          the windows and the destinations of ALL entries there - the sum of comp_len + dst_capacity is the caller's memory
+ *          bound - uploads, calls the device form and downloads out_len bytes per entry; it does not overlap the upload with
+ *          the decode.
+ * Not here the JNI natives and the Scala reader, a reader in the C++ host mirror, batching of Zstandard and encrypted streams,
+ *          the map side (s3s_cstream_*). */
+typedef struct s3s_dstream_feed_entry {
+  s3s_dstream* stream;        /* in */
+  const uint8_t* d_comp;      /* in: this stream's window, starts at s3s_dstream_position(stream) */
+  int64_t comp_len;           /* in */
+  uint8_t* d_dst;             /* in */
+  int64_t dst_capacity;       /* in */
+  s3s_dstream_result result;  /* out: exactly what a single feed fills in */
+  int32_t status;             /* out: the code a single feed would return; S3S_STATUS_NOT_RUN: see the enum */
+  int32_t pad;
+} s3s_dstream_feed_entry;
+int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_t n);
+int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_t n); /* d_comp / d_dst are HOST addresses */
 
 /* Page-locked host staging memory for the host-buffer entry points (no reference counterpart:
  * it replaces the heap byte[] of storage/S3BufferedInputStreamAdaptor.scala:13-19 — one

@@ -44,5 +44,19 @@ __device__ __forceinline__ uint32_t x8n(const uint32_t* x2n, uint64_t n, uint32_
   return p;
 }
 
+// A checksum continued: `own` is the checksum of a range of len bytes alone, `seed` the state (getValue()) in front of it; the
+// state behind it.  The identities are written out at checksum_seed_kernel (decode_stream_kernels.hip), which keeps its own copy
+// so that it stays what it was; the batched feed's seed step (decode_stream_batch.hip) calls this one.
+template <int ALGO>
+__device__ __forceinline__ int64_t checksum_continue(const Tables* __restrict__ tabs, uint64_t len, uint32_t seed, uint32_t own) {
+  if (ALGO == S3S_CHECKSUM_ADLER32) {
+    const uint64_t rem = len % kAdlerMod, a1 = seed & 0xffffu, b1 = seed >> 16, a2 = own & 0xffffu, b2 = own >> 16;
+    const uint64_t a = (a1 + a2 + kAdlerMod - 1) % kAdlerMod;
+    const uint64_t b = (rem * a1 + b1 + b2 + kAdlerMod - rem) % kAdlerMod;
+    return (int64_t)(b << 16 | a);
+  }
+  return (int64_t)(uint64_t)(multmodp(x8n(tabs->x2n, len, tabs->poly), seed, tabs->poly) ^ own);
+}
+
 }  // namespace
 }  // namespace s3s

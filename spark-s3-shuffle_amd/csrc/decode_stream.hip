@@ -724,3 +724,518 @@ int s3s_dstream_feed(s3s_dstream* s, const uint8_t* comp, int64_t comp_len, uint
 }
 
 }  // extern "C"
+
+// ---- the batched feed: one window of each of several streams per call ----------------------------------------------------
+// The path of s3s_dstream_feed_device for plain LZ4 / Snappy / LZF streams with every kernel launched once per CALL
+// (decode_stream_batch.hip) and the same three host waits whatever n is: checksums + discovery, frame tables + cut, decode.
+// Every verdict is made on the host by the single feed's rules from the same device words, and NO stream's state is committed
+// before the decode's verdict is known: when the batch's one decode status word comes back non-zero, the undecided entries go
+// through the single feed one by one, which says whose it was - nothing was committed, so its answers are the single feed's.
+namespace {
+
+struct BatchWin {         // one entry that takes part in the batched path
+  int32_t e;              // its index in the caller's array
+  int32_t n;              // pieces of partitions in its window
+  size_t piece0, seg0;    // its first piece / first checksum segment slot in the batch-wide lists (offsets: piece0 + its index)
+  bool decided = false;   // it has its verdict and has left the batch
+  int64_t n_frames = 0, stop = 0, first_frame = 0;
+  int64_t k = 0, consumed = 0, out_len = 0, need_comp = 0;
+  // the commit, made behind the decode's verdict
+  int32_t q = 0;
+  int64_t carry = 0;
+  int32_t second = -1;    // its task in the second checksum launch (the cut ended the feed inside a piece), or -1
+};
+
+}  // namespace
+
+extern "C" {
+
+int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* E, int32_t n_entries) {
+  if (!ctx) return S3S_E_INVALID;
+  ctx->err[0] = 0;
+  if (n_entries < 0 || (n_entries > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  BatchVerdict<s3s_dstream_feed_entry> verdict(E, n_entries);
+  if (n_entries == 0) return verdict.finish(S3S_OK);
+  // ---- call-level refusals: nothing has been touched ---------------------------------------------------------------------
+  bool plain = n_entries > 1 && !enc_on(ctx);
+  {
+    std::vector<const s3s_dstream*> seen;
+    seen.reserve((size_t)n_entries);
+    for (int32_t i = 0; i < n_entries; i++) {
+      const s3s_dstream* s = E[i].stream;
+      if (!s) return fail(ctx, S3S_E_INVALID, "entry %d: null stream", i);
+      if (s->ctx != ctx) return fail(ctx, S3S_E_INVALID, "entry %d: the stream was opened on another context", i);
+      if (s->codec != E[0].stream->codec || s->algo != E[0].stream->algo)
+        return fail(ctx, S3S_E_INVALID, "entry %d: the streams of a batch must share codec and checksum algorithm", i);
+      if (s->enc || s->wlog != 0 || s->codec == S3S_CODEC_NONE) plain = false;
+      seen.push_back(s);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(ctx, S3S_E_INVALID, "the same stream twice in one batch");
+  }
+  auto single = [&](s3s_dstream_feed_entry& e) {
+    e.status = s3s_dstream_feed_device(e.stream, e.d_comp, e.comp_len, e.d_dst, e.dst_capacity, &e.result);
+  };
+  auto first_error = [&]() -> int {
+    for (int32_t i = 0; i < n_entries; i++)
+      if (E[i].status != S3S_OK) {
+        char msg[sizeof ctx->err];
+        snprintf(msg, sizeof msg, "%s", ctx->err);
+        return fail(ctx, E[i].status, "entry %d of the batch failed%s%.400s", i, msg[0] ? ": " : "", msg);
+      }
+    return S3S_OK;
+  };
+  if (!plain) {  // nothing to batch: one by one, in order
+    for (int32_t i = 0; i < n_entries; i++) single(E[i]);
+    return verdict.finish(first_error());
+  }
+  const int codec = E[0].stream->codec, algo = E[0].stream->algo;
+  const bool do_sum = algo != S3S_CHECKSUM_NONE;
+  const int cf = codec == S3S_CODEC_LZF ? kChunkLzf : kChunkSnappy;
+
+  // ---- entries the single feed answers without device work keep its answer: a sticky error, an argument it refuses, an empty
+  // window.  The others are the windows of the batch
+  std::vector<BatchWin> W;
+  W.reserve((size_t)n_entries);
+  size_t P = 0, SG = 0;  // pieces and checksum segment slots of all windows
+  int64_t T = 0;         // LZ4: tiles of all windows
+  for (int32_t i = 0; i < n_entries; i++) {
+    s3s_dstream_feed_entry& e = E[i];
+    const s3s_dstream* s = e.stream;
+    const int64_t left = s->off[(size_t)s->nparts] - s->pos;
+    if (s->err != S3S_OK || e.comp_len <= 0 || e.dst_capacity < 0 || !e.d_comp || (e.dst_capacity > 0 && !e.d_dst) || e.comp_len > left) {
+      single(e);
+      continue;
+    }
+    BatchWin w;
+    w.e = i;
+    const int64_t wend = s->pos + e.comp_len;
+    int32_t n = 0;
+    while (s->cur + n < s->nparts && (s->off[(size_t)(s->cur + n)] < wend || s->off[(size_t)(s->cur + n) + 1] <= wend)) n++;
+    w.n = n;
+    w.piece0 = P;
+    w.seg0 = SG;
+    P += (size_t)n;
+    for (int32_t p = 0; p < n; p++) {
+      const int64_t a = std::max<int64_t>(s->off[(size_t)(s->cur + p)] - s->pos, 0), b = std::min(s->off[(size_t)(s->cur + p) + 1] - s->pos, e.comp_len);
+      SG += (size_t)worst_segs(b - a);
+    }
+    if (codec == S3S_CODEC_LZ4) T += lz4_tile_count(e.comp_len);
+    W.push_back(w);
+  }
+  const int32_t m = (int32_t)W.size();
+  if (m == 0) return verdict.finish(first_error());
+  if (P > 0x7fffff00ull || SG > 0x7fffff00ull || T > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "batch too large for one call");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  for (auto& v : ctx->stage_ms) v = 0;
+
+  // ---- one arena, host (pinned) and device, uploaded in one copy -----------------------------------------------------------
+  // [offsets P + m][seeds P][seg_start P + m][piece -> window P][tile -> window T][tails m][windows: LzRange m][StreamWin m]
+  // [second checksum launch: offsets 2 m | seeds m | seg_start 2 m | piece -> task m | tails m]
+  auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
+  const size_t M = (size_t)m, PM = P + M;
+  const size_t a_off = 0, a_seed = al(a_off + 8 * PM), a_seg = al(a_seed + 8 * (P + 1)), a_pw = al(a_seg + 4 * PM), a_tw = al(a_pw + 4 * (P + 1)),
+               a_tail = al(a_tw + 4 * ((size_t)T + 1)), a_rng = al(a_tail + sizeof(TaskTail) * M), a_win = al(a_rng + sizeof(LzRange) * M),
+               a_off2 = al(a_win + sizeof(StreamWin) * M), a_seed2 = al(a_off2 + 16 * M), a_seg2 = al(a_seed2 + 8 * M), a_pw2 = al(a_seg2 + 8 * M),
+               a_tail2 = al(a_pw2 + 4 * M), a_total = al(a_tail2 + sizeof(TaskTail) * M);
+  // downloads: [status words m + 1][result words kWinWords x m][sums P][second sums m]
+  const size_t h_st_o = al(a_total), h_res_o = al(h_st_o + 4 * (M + 1)), h_sum_o = al(h_res_o + 8 * kWinWords * M), h_sum2_o = al(h_sum_o + 8 * (P + 1)),
+               stage_total = al(h_sum2_o + 8 * M);
+  int rc;
+  if ((rc = ensure_stage(ctx, stage_total))) return rc;
+  if ((rc = ensure(ctx, B_PLAN, a_total))) return rc;
+  const size_t st_bytes = al(4 * (M + 1)), res_bytes = 8 * kWinWords * M;
+  if ((rc = ensure(ctx, B_STATUS, st_bytes + res_bytes + 16))) return rc;
+  if ((rc = ensure(ctx, B_SUMS, 8 * (P + M + 1)))) return rc;
+  if ((rc = ensure(ctx, B_PARTIAL, 16 * (SG > 0 ? SG : 1)))) return rc;
+  // discovery workspace per window: LZ4 4 x (tiles + 1) int64 + (tiles + 1) int32; Snappy / LZF (n + 1) int32 + (n + 2) int64
+  std::vector<size_t> ws_off(M + 1);
+  {
+    size_t w = 0;
+    for (size_t i = 0; i < M; i++) {
+      ws_off[i] = w;
+      const size_t c1 = codec == S3S_CODEC_LZ4 ? (size_t)lz4_tile_count(E[W[i].e].comp_len) + 1 : (size_t)W[i].n + 2;
+      w += al(4 * 8 * c1 + 4 * c1);
+    }
+    ws_off[M] = w;
+  }
+  if ((rc = ensure(ctx, B_PART_NFRAMES, ws_off[M] + 16))) return rc;
+  uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
+  uint8_t* da = dev<uint8_t>(ctx, B_PLAN);
+  int64_t* h_off = reinterpret_cast<int64_t*>(hs + a_off);
+  int64_t* h_seed = reinterpret_cast<int64_t*>(hs + a_seed);
+  int32_t* h_seg = reinterpret_cast<int32_t*>(hs + a_seg);
+  int32_t* h_pw = reinterpret_cast<int32_t*>(hs + a_pw);
+  int32_t* h_tw = reinterpret_cast<int32_t*>(hs + a_tw);
+  TaskTail* h_tail = reinterpret_cast<TaskTail*>(hs + a_tail);
+  LzRange* h_rng = reinterpret_cast<LzRange*>(hs + a_rng);
+  StreamWin* h_win = reinterpret_cast<StreamWin*>(hs + a_win);
+  int64_t* h_off2 = reinterpret_cast<int64_t*>(hs + a_off2);
+  int64_t* h_seed2 = reinterpret_cast<int64_t*>(hs + a_seed2);
+  int32_t* h_seg2 = reinterpret_cast<int32_t*>(hs + a_seg2);
+  int32_t* h_pw2 = reinterpret_cast<int32_t*>(hs + a_pw2);
+  TaskTail* h_tail2 = reinterpret_cast<TaskTail*>(hs + a_tail2);
+  int32_t* h_st = reinterpret_cast<int32_t*>(hs + h_st_o);
+  int64_t* h_res = reinterpret_cast<int64_t*>(hs + h_res_o);
+  int64_t* h_sums = reinterpret_cast<int64_t*>(hs + h_sum_o);
+  int64_t* h_sums2 = reinterpret_cast<int64_t*>(hs + h_sum2_o);
+  const LzRange* d_rng = reinterpret_cast<const LzRange*>(da + a_rng);
+  const StreamWin* d_win = reinterpret_cast<const StreamWin*>(da + a_win);
+  const int64_t* d_off = reinterpret_cast<const int64_t*>(da + a_off);
+  const int32_t* d_pw = reinterpret_cast<const int32_t*>(da + a_pw);
+  const int32_t* d_tw = reinterpret_cast<const int32_t*>(da + a_tw);
+  int32_t* d_status = dev<int32_t>(ctx, B_STATUS);
+  int64_t* d_result = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_STATUS) + st_bytes);
+  int64_t* d_sums = dev<int64_t>(ctx, B_SUMS);
+  int32_t* d_dec_status = d_status + m;
+
+  memset(hs + a_tail, 0, a_off2 - a_tail);
+  int32_t tile0 = 0;
+  for (int32_t wi = 0; wi < m; wi++) {
+    BatchWin& w = W[(size_t)wi];
+    const s3s_dstream_feed_entry& e = E[w.e];
+    const s3s_dstream* s = e.stream;
+    const int64_t L = e.comp_len;
+    const size_t o0 = w.piece0 + (size_t)wi;  // the window's first offset
+    int64_t segs = 0;
+    for (int32_t p = 0; p < w.n; p++) {
+      const int64_t a = s->off[(size_t)(s->cur + p)] - s->pos, b = s->off[(size_t)(s->cur + p) + 1] - s->pos;
+      h_off[o0 + (size_t)p] = a < 0 ? 0 : a;
+      h_off[o0 + (size_t)p + 1] = b < L ? b : L;
+      h_seg[o0 + (size_t)p] = (int32_t)segs;
+      segs += worst_segs(h_off[o0 + (size_t)p + 1] - h_off[o0 + (size_t)p]);
+      h_seed[w.piece0 + (size_t)p] = p == 0 ? s->carry : fresh(algo);
+      h_pw[w.piece0 + (size_t)p] = wi;
+    }
+    h_seg[o0 + (size_t)w.n] = (int32_t)segs;
+    TaskTail& t = h_tail[wi];
+    t.first_pp = (int32_t)o0;
+    t.n_parts = w.n;
+    t.first_part = (int32_t)w.piece0;
+    t.first_seg = (int32_t)w.seg0;
+    t.n_segs = (int32_t)segs;
+    t.data = e.d_comp;
+    t.data_len = L;
+    LzRange& r = h_rng[wi];
+    uint8_t* ws = dev<uint8_t>(ctx, B_PART_NFRAMES) + ws_off[(size_t)wi];
+    const int32_t nt = codec == S3S_CODEC_LZ4 ? lz4_tile_count(L) : 0;
+    const size_t c1 = codec == S3S_CODEC_LZ4 ? (size_t)nt + 1 : (size_t)w.n + 2;
+    r.comp = e.d_comp;
+    r.comp_len = L;
+    r.n_tiles = nt;
+    r.tile0 = tile0;
+    r.spec_entry = reinterpret_cast<int64_t*>(ws);
+    r.spec_exit = r.spec_entry + c1;
+    r.true_entry = r.spec_exit + c1;
+    r.frame_base = r.true_entry + c1;
+    r.spec_count = reinterpret_cast<int32_t*>(r.frame_base + c1);
+    r.status = d_status + wi;
+    r.result = d_result + (size_t)kWinWords * (size_t)wi;
+    r.dst_base = (int64_t)reinterpret_cast<uintptr_t>(e.d_dst);
+    r.dst_capacity = e.dst_capacity;
+    for (int32_t t2 = 0; t2 < nt; t2++) h_tw[tile0 + t2] = wi;
+    tile0 += nt;
+    StreamWin& x = h_win[wi];
+    x.range_left = s->off[(size_t)s->nparts] - s->pos;
+    x.last_pend = s->off[(size_t)(s->cur + w.n)] - s->pos;  // (>= L: the window cuts the last piece's partition, or ends with it)
+    x.first_piece = (int32_t)w.piece0;
+    x.n_pieces = w.n;
+    x.first_mid = s->pos > s->off[(size_t)s->cur] ? 1 : 0;  // piece 0 starts inside a codec stream
+  }
+
+  // ---- phase 1: the checksums of every piece, seeded, and stream-mode discovery of every window; one wait -------------------
+  HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, st_bytes + res_bytes, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(da, hs, a_off2, hipMemcpyHostToDevice, ctx->stream));
+  record(ctx, 0);
+  if (do_sum) {
+    launch_checksum_batch(algo, reinterpret_cast<const TaskTail*>(da + a_tail), m, (int32_t)SG, (int32_t)P, d_off,
+                          reinterpret_cast<const int32_t*>(da + a_seg), ctx->buf[B_TABLES].p, dev<uint32_t>(ctx, B_PARTIAL), d_sums, ctx->stream);
+    launch_checksum_seed_batch(algo, d_off, d_pw, (int32_t)P, ctx->buf[B_TABLES].p, reinterpret_cast<const int64_t*>(da + a_seed), d_sums,
+                               ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_sums, d_sums, 8 * P, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  record(ctx, 1);
+  if (codec == S3S_CODEC_LZ4) {
+    launch_lz4_speculate_batch(d_rng, d_tw, (int32_t)T, ctx->stream);
+    launch_lz4_resolve_stream_batch(d_rng, d_win, m, ctx->stream);
+  } else {
+    launch_snappy_count_stream_batch(d_rng, d_win, m, d_off, d_pw, (int32_t)P, cf, ctx->stream);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(h_st, d_status, st_bytes + res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+  // the single feed's verdicts, per window, from the same words
+  auto wrong_sum = [&](const BatchWin& w) -> int32_t {  // the first partition whose last byte the window holds and whose checksum is wrong, or -1
+    const s3s_dstream_feed_entry& e = E[w.e];
+    const s3s_dstream* s = e.stream;
+    if (do_sum)
+      for (int32_t i = 0; i < w.n; i++)
+        if (s->off[(size_t)(s->cur + i) + 1] <= s->pos + e.comp_len && h_sums[w.piece0 + (size_t)i] != s->ref[(size_t)(s->cur + i)]) return s->cur + i;
+    return -1;
+  };
+  auto decide = [&](BatchWin& w, int status) {
+    E[w.e].status = status;
+    w.decided = true;
+  };
+  auto corrupt = [&](BatchWin& w, const char* what) {
+    s3s_dstream_feed_entry& e = E[w.e];
+    const int32_t bad = wrong_sum(w);
+    decide(w, bad >= 0 ? stick(e.stream, &e.result, S3S_E_CHECKSUM, bad, "") : stick(e.stream, &e.result, S3S_E_BAD_FRAME, -1, what));
+  };
+  auto refused = [&](BatchWin& w, int32_t st, const char* what) {
+    if (st != S3S_E_UNSUPPORTED) return corrupt(w, what);
+    s3s_dstream_feed_entry& e = E[w.e];
+    const int32_t bad = wrong_sum(w);
+    decide(w, bad >= 0 ? stick(e.stream, &e.result, S3S_E_CHECKSUM, bad, "") : fail(ctx, S3S_E_UNSUPPORTED, "codec block larger than the decoder takes"));
+  };
+  const int64_t* h_words = h_res;  // (the status words and the result words come down in one copy: h_res_o = h_st_o + st_bytes)
+  int64_t total_frames = 0;
+  for (int32_t wi = 0; wi < m; wi++) {
+    BatchWin& w = W[(size_t)wi];
+    s3s_dstream_feed_entry& e = E[w.e];
+    memset(&e.result, 0, sizeof e.result);
+    e.result.bad_partition = -1;
+    w.first_frame = total_frames;
+    if (h_st[wi] != 0) {
+      refused(w, h_st[wi], codec == S3S_CODEC_LZ4 ? "frame chain" : "chunk chain");
+      continue;
+    }
+    const int64_t* res = h_words + (size_t)kWinWords * (size_t)wi;
+    w.stop = res[0];
+    w.need_comp = res[1];
+    w.n_frames = res[2];
+    if (w.stop < 0 || w.stop > e.comp_len || (w.stop < e.comp_len && w.need_comp <= e.comp_len - w.stop) || w.n_frames < 0) {
+      decide(w, fail(ctx, S3S_E_HIP, "frame discovery returned an impossible stop offset"));
+      w.n_frames = 0;
+      continue;
+    }
+    if (w.n_frames > 0x7fffff00ll || total_frames + w.n_frames > 0x7fffff00ll) {
+      decide(w, fail(ctx, S3S_E_UNSUPPORTED, "too many frames in one feed"));
+      w.n_frames = 0;
+      continue;
+    }
+    w.k = 0;
+    w.consumed = w.stop;
+    w.out_len = 0;
+    total_frames += w.n_frames;
+  }
+
+  // ---- phase 2: the frame records of every window, the scan of its decoded sizes, its cut at its own dst_capacity; one wait ----
+  if (total_frames > 0) {
+    const size_t nf1 = (size_t)total_frames + M + 1;
+    if ((rc = ensure(ctx, B_FRAMES, sizeof(Frame) * nf1))) return rc;
+    if ((rc = ensure(ctx, B_ITEM_SIZE, 4 * nf1))) return rc;
+    if ((rc = ensure(ctx, B_FRAME_OUT, 8 * nf1))) return rc;
+    if ((rc = ensure(ctx, B_ITEM_OFF, 8 * nf1))) return rc;
+    for (int32_t wi = 0; wi < m; wi++) {
+      const BatchWin& w = W[(size_t)wi];
+      LzRange& r = h_rng[wi];
+      const int64_t f0 = w.first_frame;
+      r.n_frames = w.decided ? 0 : w.n_frames;
+      r.skip = w.decided ? 1 : 0;
+      if (codec == S3S_CODEC_LZ4 && !w.decided) r.comp_len = w.stop;  // the one-shot emit, with the stop offset as the end of the bytes
+      r.frames = dev<Frame>(ctx, B_FRAMES) + f0;
+      r.frame_orig = dev<uint32_t>(ctx, B_ITEM_SIZE) + f0 + wi;
+      r.frame_out = dev<int64_t>(ctx, B_FRAME_OUT) + f0 + wi;
+      r.out_abs = dev<int64_t>(ctx, B_ITEM_OFF) + f0;
+      h_win[wi].stop = w.stop;
+      h_win[wi].first_frame = f0;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(da + a_rng, hs + a_rng, a_off2 - a_rng, hipMemcpyHostToDevice, ctx->stream));
+    if (codec == S3S_CODEC_LZ4) launch_lz4_emit_batch(d_rng, d_tw, (int32_t)T, ctx->stream);
+    else launch_snappy_emit_stream_batch(d_rng, d_win, m, d_off, d_pw, (int32_t)P, cf, ctx->stream);
+    launch_frames_cut_batch(codec, d_rng, d_win, m, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_st, d_status, st_bytes + res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    record(ctx, 2);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  int32_t n_second = 0;
+  bool any_decode = false;
+  for (int32_t wi = 0; wi < m; wi++) {
+    BatchWin& w = W[(size_t)wi];
+    if (w.decided) continue;
+    s3s_dstream_feed_entry& e = E[w.e];
+    s3s_dstream* s = e.stream;
+    if (w.n_frames > 0) {
+      if (h_st[wi] != 0) {
+        refused(w, h_st[wi], "frame header");
+        continue;
+      }
+      const int64_t* res = h_words + (size_t)kWinWords * (size_t)wi;
+      w.k = res[4];
+      w.consumed = res[5];
+      w.out_len = res[6];
+      if (w.k < 0 || w.k > w.n_frames || w.consumed < 0 || w.consumed > w.stop || w.out_len < 0 || w.out_len > e.dst_capacity) {
+        decide(w, fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible frame index"));
+        continue;
+      }
+      if (w.consumed == 0) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
+        e.result.need_dst = res[7];
+        decide(w, fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld decoded bytes of the next unit", (long long)e.dst_capacity, (long long)res[7]));
+        continue;
+      }
+    }
+    // the verdict of every partition whose last byte this feed consumes, before anything is decoded
+    const int64_t new_pos = s->pos + w.consumed;
+    int32_t q = s->cur;
+    bool bad = false;
+    for (; q < s->nparts && s->off[(size_t)q + 1] <= new_pos; q++)
+      if (do_sum && h_sums[w.piece0 + (size_t)(q - s->cur)] != s->ref[(size_t)q]) {
+        decide(w, stick(s, &e.result, S3S_E_CHECKSUM, q, ""));
+        bad = true;
+        break;
+      }
+    if (bad) continue;
+    // the state of the partition left open: known already unless the capacity cut ended the feed inside its piece
+    w.q = q;
+    w.carry = fresh(algo);
+    if (do_sum && q < s->nparts) {
+      const int32_t i = q - s->cur;
+      const int64_t seed = i == 0 ? s->carry : fresh(algo);
+      const int64_t* po = h_off + w.piece0 + (size_t)wi;
+      if (i >= w.n || w.consumed <= po[i]) w.carry = seed;
+      else if (w.consumed == po[i + 1]) w.carry = h_sums[w.piece0 + (size_t)i];
+      else {
+        const int32_t t = n_second++;
+        w.second = t;
+        h_off2[2 * t] = po[i];
+        h_off2[2 * t + 1] = w.consumed;
+        h_seg2[2 * t] = 0;
+        h_seg2[2 * t + 1] = worst_segs(w.consumed - po[i]);
+        h_seed2[t] = seed;
+        h_pw2[t] = t;
+        TaskTail& tt = h_tail2[t];
+        memset(&tt, 0, sizeof tt);
+        tt.first_pp = 2 * t;
+        tt.n_parts = 1;
+        tt.first_part = t;
+        tt.n_segs = h_seg2[2 * t + 1];
+        tt.data = e.d_comp;
+        tt.data_len = e.comp_len;
+      }
+    }
+    if (w.k > 0) any_decode = true;
+  }
+
+  // ---- phase 3: one decode launch over the frames of all windows in front of their cuts; one wait ---------------------------
+  if (any_decode || n_second > 0) {
+    if (any_decode) {
+      for (int32_t wi = 0; wi < m; wi++) h_rng[wi].skip = W[(size_t)wi].decided ? 1 : 0;
+      HIP_TRY(ctx, hipMemcpyAsync(da + a_rng, hs + a_rng, sizeof(LzRange) * M, hipMemcpyHostToDevice, ctx->stream));
+      launch_frames_rebase_cut(d_rng, d_win, m, total_frames, ctx->stream);
+      if (codec == S3S_CODEC_LZ4)
+        launch_lz4_decompress(nullptr, dev<Frame>(ctx, B_FRAMES), (int32_t)total_frames, dev<int64_t>(ctx, B_ITEM_OFF), nullptr, d_dec_status,
+                              ctx->lz4_decode_variant, ctx->stream);
+      else
+        launch_snappy_decompress(nullptr, dev<Frame>(ctx, B_FRAMES), (int32_t)total_frames, dev<int64_t>(ctx, B_ITEM_OFF), nullptr, d_dec_status,
+                                 ctx->lz4_decode_variant, ctx->stream, cf);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_second > 0) {  // the pieces the cuts left open, summed up to the cut: one launch for all of them
+      int32_t seg0 = 0;
+      for (int32_t t = 0; t < n_second; t++) {
+        h_tail2[t].first_seg = seg0;
+        seg0 += h_tail2[t].n_segs;
+      }
+      HIP_TRY(ctx, hipMemcpyAsync(da + a_off2, hs + a_off2, a_total - a_off2, hipMemcpyHostToDevice, ctx->stream));
+      launch_checksum_batch(algo, reinterpret_cast<const TaskTail*>(da + a_tail2), n_second, seg0, n_second,
+                            reinterpret_cast<const int64_t*>(da + a_off2), reinterpret_cast<const int32_t*>(da + a_seg2), ctx->buf[B_TABLES].p,
+                            dev<uint32_t>(ctx, B_PARTIAL), d_sums + P, ctx->stream);
+      launch_checksum_seed_batch(algo, reinterpret_cast<const int64_t*>(da + a_off2), reinterpret_cast<const int32_t*>(da + a_pw2), n_second,
+                                 ctx->buf[B_TABLES].p, reinterpret_cast<const int64_t*>(da + a_seed2), d_sums + P, ctx->stream);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(h_sums2, d_sums + P, 8 * (size_t)n_second, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    record(ctx, 3);
+    HIP_TRY(ctx, hipMemcpyAsync(&h_st[m], d_dec_status, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->profile) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]) == hipSuccess) ctx->stage_ms[S3S_STAGE_TOTAL] = ms;
+      if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->stage_ms[S3S_STAGE_CHECKSUM] = ms;
+      if (total_frames > 0 && hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]) == hipSuccess) ctx->stage_ms[S3S_STAGE_DISCOVER] = ms;
+      if (total_frames > 0 && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->stage_ms[S3S_STAGE_CODEC] = ms;
+    }
+    if (any_decode && h_st[m] != 0) {
+      // some frame of the batch is corrupt, or an LZ4 frame is above 32 MiB: nothing was committed, so the single feed answers
+      // for every undecided entry (and runs the ring decoder where that is what the frame needs)
+      std::vector<int32_t> todo;
+      for (const BatchWin& w : W)
+        if (!w.decided) todo.push_back(w.e);
+      for (int32_t i : todo) single(E[i]);
+      return verdict.finish(first_error());
+    }
+  }
+
+  // ---- commit -------------------------------------------------------------------------------------------------------------
+  for (BatchWin& w : W) {
+    if (w.decided) continue;
+    s3s_dstream_feed_entry& e = E[w.e];
+    s3s_dstream* s = e.stream;
+    s->pos += w.consumed;
+    s->cur = w.q;
+    s->carry = w.second >= 0 ? h_sums2[w.second] : w.carry;
+    e.result.consumed = w.consumed;
+    e.result.out_len = w.out_len;
+    e.result.need_comp = w.consumed == 0 ? w.need_comp : 0;
+    e.result.at_end = at_end(s);
+    e.status = S3S_OK;
+  }
+  return verdict.finish(first_error());
+}
+
+int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* E, int32_t n_entries) {
+  if (!ctx) return S3S_E_INVALID;
+  ctx->err[0] = 0;
+  if (n_entries < 0 || (n_entries > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  BatchVerdict<s3s_dstream_feed_entry> verdict(E, n_entries);
+  if (n_entries == 0) return verdict.finish(S3S_OK);
+  // the windows and the destinations of ALL entries are staged in the context's workspace: the sum of comp_len + dst_capacity
+  // is the caller's memory bound.  An entry the single feed refuses by its arguments is staged as empty and keeps them
+  auto al = [](int64_t x) { return (x + 255) & ~int64_t(255); };
+  std::vector<s3s_dstream_feed_entry> D(E, E + n_entries);
+  std::vector<int64_t> so((size_t)n_entries), dso((size_t)n_entries);
+  int64_t src_total = 0, dst_total = 0;
+  for (int32_t i = 0; i < n_entries; i++) {
+    const s3s_dstream_feed_entry& e = E[i];
+    const bool ok = e.comp_len >= 0 && e.dst_capacity >= 0 && (e.comp_len == 0 || e.d_comp) && (e.dst_capacity == 0 || e.d_dst);
+    so[(size_t)i] = src_total;
+    dso[(size_t)i] = dst_total;
+    if (ok) {
+      src_total += al(e.comp_len + 64);
+      dst_total += al(e.dst_capacity + 64);
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = ensure(ctx, B_SRC, (size_t)src_total + 64))) return rc;
+  if ((rc = ensure(ctx, B_DST, (size_t)dst_total + 64))) return rc;
+  for (int32_t i = 0; i < n_entries; i++) {
+    const s3s_dstream_feed_entry& e = E[i];
+    const bool ok = e.comp_len >= 0 && e.dst_capacity >= 0 && (e.comp_len == 0 || e.d_comp) && (e.dst_capacity == 0 || e.d_dst);
+    if (!ok) {  // the device form's single feed answers S3S_E_INVALID from the same arguments (a null pointer stays null)
+      D[(size_t)i].d_comp = e.d_comp ? dev<uint8_t>(ctx, B_SRC) : nullptr;
+      D[(size_t)i].d_dst = e.d_dst ? dev<uint8_t>(ctx, B_DST) : nullptr;
+      continue;
+    }
+    D[(size_t)i].d_comp = dev<uint8_t>(ctx, B_SRC) + so[(size_t)i];
+    D[(size_t)i].d_dst = dev<uint8_t>(ctx, B_DST) + dso[(size_t)i];
+    if (e.comp_len > 0 && e.stream && e.stream->err == S3S_OK)
+      HIP_TRY(ctx, hipMemcpyAsync(dev<uint8_t>(ctx, B_SRC) + so[(size_t)i], e.d_comp, (size_t)e.comp_len, hipMemcpyHostToDevice, ctx->stream));
+  }
+  rc = s3s_dstream_feed_batch_device(ctx, D.data(), n_entries);
+  for (int32_t i = 0; i < n_entries; i++) {
+    E[i].result = D[(size_t)i].result;
+    E[i].status = D[(size_t)i].status;
+  }
+  for (int32_t i = 0; i < n_entries; i++)
+    if (E[i].status == S3S_OK && E[i].result.out_len > 0)
+      HIP_TRY(ctx, hipMemcpyAsync(E[i].d_dst, D[(size_t)i].d_dst, (size_t)E[i].result.out_len, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return verdict.finish(rc);
+}
+
+}  // extern "C"

@@ -4,7 +4,8 @@
 //
 // These are the one-shot discovery walks (lz4_decompress.hip, snappy_decompress.hip) and the checksum combine (checksum.hip)
 // with one rule added each; they live in a file of their own so that the kernels the one-shot entry points launch stay what
-// they were, instruction for instruction.  The header checks and the polynomial arithmetic are shared (discover_core.h,
+// they were, instruction for instruction.  The header checks, the stream-mode walks (walk_tile_stream, walk_piece_stream: the
+// batched feed's kernels, decode_stream_batch.hip, run them too) and the polynomial arithmetic are shared (discover_core.h,
 // checksum_core.h).
 #include "s3s_internal.h"
 #include "checksum_core.h"
@@ -12,36 +13,6 @@
 
 namespace s3s {
 namespace {
-
-// ---- stream mode (s3s_dstream_feed*): the window comp[0, comp_len) may end inside a frame ---------------------------------
-// walk_tile with the stop rule: a frame whose header or payload crosses comp_len ends the chain (*need = its length as far
-// as the window shows it, the return value = where it starts) unless it crosses range_left too - then the RANGE ends
-// inside it, which is the one-shot walk's "Stream ended prematurely".  A header is read only when all 21 bytes of it lie
-// in front of comp_len.  Counts only: the frames are emitted by the one-shot tile_emit_kernel up to the stop offset.
-__device__ int64_t walk_tile_stream(const uint8_t* comp, int64_t comp_len, int64_t range_left, int64_t pos, int64_t tile_end,
-                                    int32_t* count_out, int64_t* need) {
-  int32_t n = 0;
-  *need = 0;
-  while (pos < tile_end && pos < comp_len) {
-    int64_t unit = kLz4FrameHeader;
-    if (comp_len - pos >= kLz4FrameHeader) {
-      const uint8_t* h = comp + pos;
-      if (ld64u(h) != kMagic) return -1;
-      const Header hd = parse_header(h);
-      if (!hd.ok) return -1;
-      unit += hd.comp_len;
-    }
-    if (unit > range_left - pos) return -1;
-    if (unit > comp_len - pos) {
-      *need = unit;
-      break;
-    }
-    n++;
-    pos += unit;
-  }
-  *count_out = n;
-  return pos;
-}
 
 // resolve_chain (lz4_decompress.hip) with the stop rule and the result words.  The speculation in front of it is the one-shot
 // kernel: a tile that holds the cut frame has no speculative exit, so it is re-walked here.
@@ -129,100 +100,6 @@ __global__ __launch_bounds__(256) void frames_cut_kernel(const Frame* __restrict
   result[1] = consumed;
   result[2] = o;
   result[3] = need;
-}
-
-// ---- stream mode (s3s_dstream_feed*): pieces of partitions inside a window that may end inside a unit -------------------
-// One piece [beg, end) of a partition that ends at pend >= end (pend > end: the window ends first).  A unit - a stream
-// header, a length | chunk, a ZV chunk - is read only when it lies in front of `end`; one that does not fit in front of
-// pend is the one-shot walk's corruption (-1), one that fits there but not in front of `end` ends the walk: *stop = where
-// it starts, *need = its length as far as the piece shows it (the header's when the header is cut, then header + payload).
-// mid: the piece starts inside a Snappy stream, so no stream header is expected at beg.  Returns the chunks in front of *stop.
-// A Snappy chunk whose varint claims more than kBatchMaxBlock decoded bytes ends the walk with -2: no decoder takes it, and a
-// caller must not be sent for a buffer of that size (need_dst) - an LZ4Block frame is bounded by parse_header, an LZF chunk by
-// its 16-bit field, a Snappy varint by nothing.
-struct PieceWalk {
-  int64_t ip, end, pend, need;
-  // 0: x more bytes are there; 1: the window ends first (need set); -1: the partition ends first
-  __device__ __forceinline__ int want(int64_t x) {
-    if (x > pend - ip) return -1;
-    if (x > end - ip) {
-      need = x;
-      return 1;
-    }
-    return 0;
-  }
-};
-
-__device__ int walk_piece_stream(const uint8_t* comp, int64_t beg, int64_t end, int64_t pend, bool mid, int chunk_format, bool emit,
-                                 Frame* frames, uint32_t* frame_orig, int64_t* stop, int64_t* need) {
-  PieceWalk w{beg, end, pend, 0};
-  int n = 0;
-  bool header_next = !mid && chunk_format != kChunkLzf;
-  while (w.ip < end) {
-    int r;
-    Frame f;
-    int64_t unit;
-    if (chunk_format == kChunkLzf) {
-      if ((r = w.want(5)) != 0) { if (r < 0) return -1; break; }
-      if (comp[w.ip] != 'Z' || comp[w.ip + 1] != 'V' || comp[w.ip + 2] > 1) return -1;
-      const int type = comp[w.ip + 2];
-      const uint32_t len = (uint32_t)comp[w.ip + 3] << 8 | comp[w.ip + 4];
-      const int head = type == 1 ? 7 : 5;
-      uint32_t ulen = len;
-      if (type == 1) {
-        if ((r = w.want(7)) != 0) { if (r < 0) return -1; break; }
-        ulen = (uint32_t)comp[w.ip + 5] << 8 | comp[w.ip + 6];
-        if (len == 0 || ulen == 0) return -1;
-      }
-      unit = head + (int64_t)len;
-      if ((r = w.want(unit)) != 0) { if (r < 0) return -1; break; }
-      f = Frame{w.ip + head, (int32_t)len, (int32_t)ulen, 0u, type == 1 ? 2 : 0x10};
-    } else {
-      if (header_next) {
-        if ((r = w.want(kSnappyStreamHeader)) != 0) { if (r < 0) return -1; break; }
-        if (!is_stream_header(comp + w.ip)) return -1;
-        w.ip += kSnappyStreamHeader;
-        header_next = false;
-        continue;
-      }
-      if ((r = w.want(4)) != 0) { if (r < 0) return -1; break; }
-      const uint32_t cl = (uint32_t)comp[w.ip] << 24 | (uint32_t)comp[w.ip + 1] << 16 | (uint32_t)comp[w.ip + 2] << 8 |
-                          (uint32_t)comp[w.ip + 3];
-      if (cl == 0x82534e41u) {  // the next concatenated stream starts here
-        header_next = true;
-        continue;
-      }
-      if (cl == 0) return -1;
-      unit = 4 + (int64_t)cl;
-      if ((r = w.want(unit)) != 0) { if (r < 0) return -1; break; }
-      uint32_t ulen = 0;
-      int sh = 0;
-      for (uint32_t i = 0;; i++, sh += 7) {
-        if (i >= cl || sh > 28) return -1;
-        const uint32_t b = comp[w.ip + 4 + i];
-        ulen |= (b & 0x7fu) << sh;
-        if (!(b & 0x80u)) break;
-      }
-      if (ulen > (uint32_t)kBatchMaxBlock) return -2;
-      f = Frame{w.ip + 4, (int32_t)cl, (int32_t)ulen, 0u, 1};
-    }
-    if (emit) {
-      frames[n] = f;
-      frame_orig[n] = (uint32_t)f.orig_len;
-    }
-    n++;
-    w.ip += unit;
-  }
-  *stop = w.ip;
-  *need = w.need;
-  return n;
-}
-
-// One lane per piece raises the window's status word, so the word must not depend on which lane comes last: corruption in any
-// piece (-1) is S3S_E_BAD_FRAME whatever the other pieces say, a refused claim (-2) is written only over "no error".
-__device__ __forceinline__ void raise_piece_status(int32_t* status, int n) {
-  if (n == -2) atomicCAS(status, 0, S3S_E_UNSUPPORTED);
-  else atomicExch(status, S3S_E_BAD_FRAME);
 }
 
 // result (written for the LAST piece, the only one a window can cut): [0] = stop offset, [1] = need

@@ -215,35 +215,6 @@ __global__ __launch_bounds__(kWave) void tile_emit_batch_kernel(const LzRange* _
   emit_tile(r.comp, r.comp_len, b - r.tile0, r.true_entry, r.frame_base, r.frames, r.frame_orig, r.status);
 }
 
-// generic exclusive scan of uint32 -> int64 (n+1 outputs): ONE wavefront, NO LDS — the decode kernels of
-// the other task threads book the whole LDS of every CU (20 x 8 KiB rings), and a workgroup that needs
-// any of it waits for one of their frames to finish (see scan_items_kernel in assemble.hip)
-__device__ __forceinline__ void scan_u32_wave(const uint32_t* __restrict__ in, int64_t n, int64_t* __restrict__ out,
-                                              int lane) {
-  int64_t carry = 0;
-  for (int64_t tile = 0; tile < n; tile += 4 * kWave) {
-    const int64_t i0 = tile + 4 * lane;
-    int64_t x[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) x[k] = i0 + k < n ? (int64_t)in[i0 + k] : 0;
-    const int64_t mine = x[0] + x[1] + x[2] + x[3];
-    int64_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int64_t y = __shfl_up(inc, d);
-      if (lane >= d) inc += y;
-    }
-    int64_t off = carry + inc - mine;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (i0 + k < n) out[i0 + k] = off;
-      off += x[k];
-    }
-    carry += __shfl(inc, kWave - 1);
-  }
-  if (lane == 0) out[n] = carry;
-}
-
 __global__ __launch_bounds__(kWave) void scan_u32_kernel(const uint32_t* __restrict__ in, int64_t n,
                                                          int64_t* __restrict__ out) {
   scan_u32_wave(in, n, out, threadIdx.x);
@@ -652,6 +623,20 @@ void launch_lz4_frames_batch(LzRange* d_ranges, int32_t n_ranges, const int32_t*
                        d_ranges, d_tile_range, total_tiles);
   if (n_ranges > 0)
     hipLaunchKernelGGL(frames_finish_batch_kernel, dim3((unsigned)n_ranges), dim3(kWave), 0, st, d_ranges, n_ranges);
+}
+
+// the two per-tile launches of the batched call on their own: the batched feed (decode_stream_batch.hip) puts its own
+// per-window kernels behind them
+void launch_lz4_speculate_batch(const LzRange* d_ranges, const int32_t* d_tile_range, int32_t total_tiles, hipStream_t st) {
+  if (total_tiles > 0)
+    hipLaunchKernelGGL(tile_speculate_batch_kernel, dim3((unsigned)total_tiles), dim3(kWave), 0, st, d_ranges,
+                       d_tile_range, total_tiles);
+}
+
+void launch_lz4_emit_batch(const LzRange* d_ranges, const int32_t* d_tile_range, int32_t total_tiles, hipStream_t st) {
+  if (total_tiles > 0)
+    hipLaunchKernelGGL(tile_emit_batch_kernel, dim3((unsigned)((total_tiles + kWave - 1) / kWave)), dim3(kWave), 0, st,
+                       d_ranges, d_tile_range, total_tiles);
 }
 
 void launch_scan_u32(const uint32_t* d_in, int64_t n, int64_t* d_out, hipStream_t st) {

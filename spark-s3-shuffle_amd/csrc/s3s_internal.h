@@ -317,6 +317,39 @@ void launch_frames_cut(int codec, const Frame* d_frames, const uint32_t* d_frame
 void launch_checksum_seed(int algo, const int64_t* d_offsets, int32_t n, const void* d_tables, const int64_t* d_seeds,
                           int64_t* d_out, hipStream_t st);
 
+// ---- batched feed (decode_stream.hip: s3s_dstream_feed_batch*; kernels: decode_stream_batch.hip) ---------------------------
+// One window of each of several streams per call.  A window is an LzRange - comp / comp_len = the window, status = its status
+// word, result = its kWinWords result words ([0] stop, [1] need, [2] frames in front of the stop; [4] k, [5] consumed,
+// [6] out_len, [7] decoded bytes of frame k), spec_count / frame_base = per tile (LZ4) or per piece (Snappy, LZF) - plus a
+// StreamWin.  The kernels are the single feed's with the window found through the descriptors; each is ONE launch per call.
+constexpr int kWinWords = 8;
+struct StreamWin {
+  int64_t range_left;    // LZ4: what the range still holds from the window's start (launch_lz4_discover_stream)
+  int64_t last_pend;     // Snappy / LZF: where the last piece's partition ends (launch_snappy_count_frames_stream)
+  int32_t first_piece;   // the window's first piece in the batch-wide piece list; it owns n_pieces + 1 consecutive offsets,
+  int32_t n_pieces;      // so its offsets start at first_piece + the window's index
+  int32_t first_mid, pad;
+  int64_t stop;          // phase 2: the stop offset discovery returned
+  int64_t first_frame;   // phase 2: the window's first frame in the batch-wide frame table
+};
+//   the per-tile launches of launch_lz4_discover_batch / launch_lz4_frames_batch on their own (lz4_decompress.hip)
+void launch_lz4_speculate_batch(const LzRange* d_ranges, const int32_t* d_tile_range, int32_t total_tiles, hipStream_t st);
+void launch_lz4_emit_batch(const LzRange* d_ranges, const int32_t* d_tile_range, int32_t total_tiles, hipStream_t st);
+//   LZ4: one wavefront per window resolves the chain with the stop rule and scans the tile counts
+void launch_lz4_resolve_stream_batch(const LzRange* d_ranges, const StreamWin* d_wins, int32_t n_wins, hipStream_t st);
+//   Snappy / LZF: one lane per piece of every window (d_piece_win: piece -> window); count is followed by the per-window scan
+void launch_snappy_count_stream_batch(const LzRange* d_ranges, const StreamWin* d_wins, int32_t n_wins, const int64_t* d_piece_off,
+                                      const int32_t* d_piece_win, int32_t total_pieces, int chunk_format, hipStream_t st);
+void launch_snappy_emit_stream_batch(const LzRange* d_ranges, const StreamWin* d_wins, int32_t n_wins, const int64_t* d_piece_off,
+                                     const int32_t* d_piece_win, int32_t total_pieces, int chunk_format, hipStream_t st);
+//   the scan of every window's decoded sizes and its cut at its own dst_capacity (launch_frames_cut per window)
+void launch_frames_cut_batch(int codec, const LzRange* d_ranges, const StreamWin* d_wins, int32_t n_wins, hipStream_t st);
+//   absolute addresses for the frames in front of every window's cut, empty frames behind it and for a window with skip set
+void launch_frames_rebase_cut(const LzRange* d_ranges, const StreamWin* d_wins, int32_t n_wins, int64_t total_frames, hipStream_t st);
+//   launch_checksum_seed over the flattened piece table (d_offsets: n_pieces + 1 per window, d_seeds / d_out: one per piece)
+void launch_checksum_seed_batch(int algo, const int64_t* d_offsets, const int32_t* d_piece_win, int32_t total_pieces,
+                                const void* d_tables, const int64_t* d_seeds, int64_t* d_out, hipStream_t st);
+
 // ---- streaming map side (compress_stream.hip: s3s_cstream_feed*) -----------------------------------------------------------
 //   The cut of a window's plan at the caller's output capacity, behind the scan of the item sizes (compress_stream_kernels.hip;
 //   the arithmetic is compress_stream_core.h).  d_marks: one s3s_cs::Mark per item; d_part_first[n_pieces + 1]: first item of

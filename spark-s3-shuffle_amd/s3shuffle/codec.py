@@ -88,6 +88,12 @@ class StreamResult(ctypes.Structure):
                 ("need_dst", ctypes.c_int64), ("bad_partition", ctypes.c_int32), ("at_end", ctypes.c_int32)]
 
 
+class FeedEntry(ctypes.Structure):
+    """s3s_dstream_feed_entry (include/s3shuffle_codec.h): one stream's window in a batched feed."""
+    _fields_ = [("stream", ctypes.c_void_p), ("d_comp", ctypes.c_void_p), ("comp_len", ctypes.c_int64), ("d_dst", ctypes.c_void_p),
+                ("dst_capacity", ctypes.c_int64), ("result", StreamResult), ("status", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class CompressStreamResult(ctypes.Structure):
     """s3s_cstream_result (include/s3shuffle_codec.h): what one feed of a CompressStream did."""
     _fields_ = [("consumed", ctypes.c_int64), ("out_len", ctypes.c_int64), ("need_src", ctypes.c_int64),
@@ -196,6 +202,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "s3s_dstream_held_bytes"):  # debug accessor: device bytes a stream (or, with NULL, all streams) holds between feeds
         lib.s3s_dstream_held_bytes.restype = ctypes.c_int64
         lib.s3s_dstream_held_bytes.argtypes = [vp]
+    if hasattr(lib, "s3s_dstream_feed_batch_device"):  # the batched feed (additive, detected by the symbols)
+        lib.s3s_dstream_feed_batch_device.argtypes = [vp, ctypes.POINTER(FeedEntry), ctypes.c_int32]
+        lib.s3s_dstream_feed_batch.argtypes = lib.s3s_dstream_feed_batch_device.argtypes
     _LIB = lib
     return lib
 
@@ -447,6 +456,47 @@ class Codec:
         `window_log_max` (10 .. 27, with ZSTD): a resumable Zstandard stream through s3s_dstream_open_zstd, which keeps at most
         1 << window_log_max bytes of history on the device for its open frame."""
         return DecodeStream(self, codec, checksum, part_offsets, ref_checksums, encrypted=encrypted, window_log_max=window_log_max)
+
+    def feed_streams_device(self, entries, _host: bool = False):
+        """The batched feed (s3s_dstream_feed_batch_device): `entries` = [(DecodeStream, d_comp, comp_len, d_dst, dst_capacity),
+        ...], one window of each of several streams of this context -> per entry (status, StreamResult), each what
+        `stream.feed_device` alone would have given.  Nothing is raised for an entry's own verdict; `last_batch_code` is the
+        call's return code (the first entry's that is not S3S_OK, or S3S_E_INVALID with every entry S3S_STATUS_NOT_RUN)."""
+        if not hasattr(self._lib, "s3s_dstream_feed_batch_device"):
+            raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_dstream_feed_batch_device")
+        arr = (FeedEntry * max(len(entries), 1))()
+        for i, (stream, d_comp, comp_len, d_dst, cap) in enumerate(entries):
+            arr[i].stream = getattr(stream, "_s", stream)  # a DecodeStream, or a raw handle (None: a null stream)
+            arr[i].d_comp = d_comp if comp_len else None
+            arr[i].comp_len = int(comp_len)
+            arr[i].d_dst = d_dst if cap else None
+            arr[i].dst_capacity = int(cap)
+        fn = self._lib.s3s_dstream_feed_batch if _host else self._lib.s3s_dstream_feed_batch_device
+        self.last_batch_code = int(fn(self._h, arr, len(entries)))
+        out = []
+        for i, e in enumerate(entries):
+            r = StreamResult.from_buffer_copy(arr[i].result)
+            r.code = int(arr[i].status)
+            if hasattr(e[0], "last_result"):
+                e[0].last_result = r
+            out.append((r.code, r))
+        return out
+
+    def feed_streams(self, entries):
+        """The host-buffer form (s3s_dstream_feed_batch): `entries` = [(DecodeStream, comp, dst), ...] or
+        [(DecodeStream, comp, dst, dst_capacity), ...] with uint8 arrays; the decoded bytes land in dst[:result.out_len].  The
+        library stages the windows and destinations of ALL entries on the device: the sum of their sizes is the memory bound."""
+        rows, keep = [], []
+        for e in entries:
+            stream, comp, dst = e[0], np.ascontiguousarray(e[1], dtype=np.uint8), e[2]
+            if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable):
+                raise ValueError("dst must be a writable C-contiguous uint8 array (the library writes into it)")
+            cap = dst.size if len(e) < 4 or e[3] is None else int(e[3])
+            if not 0 <= cap <= dst.size:
+                raise ValueError(f"dst_capacity {cap} is outside dst's {dst.size} bytes")
+            keep.append(comp)
+            rows.append((stream, comp.ctypes.data, comp.size, dst.ctypes.data, cap))
+        return self.feed_streams_device(rows, _host=True)
 
     def decompressed_size(self, codec: int, comp: np.ndarray) -> int:
         comp = np.ascontiguousarray(comp, dtype=np.uint8)
