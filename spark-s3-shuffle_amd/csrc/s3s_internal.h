@@ -284,7 +284,7 @@ void launch_snappy_decompress(const uint8_t* d_comp, const Frame* d_frames, int3
                               int variant, hipStream_t st, int chunk_format = kChunkSnappy);
 void launch_scan_u32(const uint32_t* d_in, int64_t n, int64_t* d_out, hipStream_t st);
 
-// ---- streaming reduce side (decode_stream.hip: s3s_dstream_feed*) ----------------------------------------------------------
+// ---- streaming reduce side (decode_stream.hip: s3s_dstream_feed*; its host rules: decode_stream_core.h) ---------------------
 // The window comp[0, comp_len) starts on a unit boundary of the range and may end inside a unit; range_left >= comp_len is
 // what the RANGE still holds from the window's start.  A unit that crosses comp_len ends the chain there (d_result[0] = the
 // stop offset, d_result[1] = the unit's length as far as the window shows it: header + payload when the header is whole,
@@ -317,7 +317,7 @@ void launch_frames_cut(int codec, const Frame* d_frames, const uint32_t* d_frame
 void launch_checksum_seed(int algo, const int64_t* d_offsets, int32_t n, const void* d_tables, const int64_t* d_seeds,
                           int64_t* d_out, hipStream_t st);
 
-// ---- batched feed (decode_stream.hip: s3s_dstream_feed_batch*; kernels: decode_stream_batch.hip) ---------------------------
+// ---- batched feed (decode_stream.hip: s3s_dstream_feed_batch*, the same host rules; kernels: decode_stream_batch.hip) ------
 // One window of each of several streams per call.  A window is an LzRange - comp / comp_len = the window, status = its status
 // word, result = its kWinWords result words ([0] stop, [1] need, [2] frames in front of the stop; [4] k, [5] consumed,
 // [6] out_len, [7] decoded bytes of frame k), spec_count / frame_base = per tile (LZ4) or per piece (Snappy, LZF) - plus a
