@@ -237,6 +237,13 @@ enum { S3S_OPT_ZSTD_DECODE_STAGED = 15, /* ABI 11, additive; tuning, identical o
                                     on this context whose frames completed on the staged path of key 15 (frames in partitions
                                     that decoded), 0 otherwise; key 14 keeps counting the block path of key 13 only.
                                     s3s_set_option on it answers S3S_E_INVALID */
+  , S3S_OPT_DSTREAM_BATCH_ENTRIES = 17 /* (not at the start of a line either) ABI 11, additive, READ-ONLY: the number of entries of
+                                    the context's last s3s_dstream_feed_batch* call whose answer came from the batched path (its
+                                    three phases); 0 when the call fell back to single feeds or was refused.  Entries that the
+                                    single feed answered inside the call - without device work, or again after a bad decode
+                                    status - are not counted.  s3s_set_option on it answers S3S_E_INVALID; a library without the
+                                    key answers S3S_E_INVALID to reading it, which is how a caller detects that encrypted
+                                    streams are batched */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */
@@ -694,7 +701,7 @@ int64_t s3s_cstream_position(const s3s_cstream* s); /* source bytes consumed so 
 int64_t s3s_cstream_written(const s3s_cstream* s);  /* image bytes produced so far = image offset of the next feed's dst */
 int s3s_cstream_close(s3s_cstream* s);
 
-/* ---- reduce side, streaming: the batched feed (ABI 11, additive: callers detect support by the symbol; no option key) ------
+/* ---- reduce side, streaming: the batched feed (ABI 11, additive: callers detect support by the symbol; encrypted streams: key 17) --
  * The reference's reduce task never reads one stream at a time: S3BufferedPrefetchIterator keeps up to
  * spark.shuffle.s3.maxConcurrencyTask (10) fetches open, each behind a buffer of spark.shuffle.s3.bufferSize (8 MiB), together
  * under spark.shuffle.s3.maxBufferSizeTask (128 MiB) - S3ShuffleDispatcher.scala:55-57.  A feed has a floor of about half a
@@ -713,20 +720,31 @@ int s3s_cstream_close(s3s_cstream* s);
  *          or checksum algorithm.  n == 0 is S3S_OK.
  * Caller   promises that the windows and the destinations of different entries do not overlap each other; the library does
  *          not check it.
- * Batched  plain LZ4, Snappy and LZF streams: three host waits per call whatever n is (checksums + discovery; frame tables +
- *          the cut of every window at its own dst_capacity; one decode launch over the frames of all windows), and no stream's
- *          state is committed before the decode's verdict is known.  When that verdict is bad - a corrupt payload, or an LZ4
- *          frame above 32 MiB that needs the ring decoder - the undecided entries are fed one by one through the single feed,
- *          which says whose it was.  S3S_OPT_LZ4_DECODE_VARIANT is honoured.
+ * Batched  LZ4, Snappy and LZF streams, n > 1, all of them plain (s3s_dstream_open, no IO encryption on the context) or all of
+ *          them encrypted (s3s_dstream_open_encrypted, ABI 11 with key 17, under the context's current key): three host waits
+ *          per call whatever n is (checksums + discovery; frame tables + the cut of every window at its own dst_capacity; one
+ *          decode launch over the frames of all windows), and no stream's state is committed before the decode's verdict is
+ *          known.  When that verdict is bad - a corrupt payload, or an LZ4 frame above 32 MiB that needs the ring decoder - the
+ *          undecided entries are fed one by one through the single feed, which says whose it was.
+ *          S3S_OPT_LZ4_DECODE_VARIANT is honoured.  Encrypted: ONE launch of the window form of the AES-CTR pass decrypts the
+ *          windows of all entries in front of discovery, each into a plain buffer of its own, and gathers their IVs, which
+ *          come back with the first wait; the stored side (checksums, consumed, need_comp, the position) and the plain side
+ *          (discovery, the cut, the decoders) are those of the single feed, window by window.  An entry whose stream is bound
+ *          to an earlier key setting, or a plain stream on a context with the layer on, gets the single feed's refusal
+ *          (S3S_E_INVALID / S3S_E_UNSUPPORTED) as its own status; the other entries run batched.
  * One by one, in order, through the single feed inside the call (the contract holds for every stream the library can open):
- *          n == 1, S3S_CODEC_NONE, any stream of s3s_dstream_open_encrypted or s3s_dstream_open_zstd, a context with IO
- *          encryption on.
- * Memory   the device form works in the context's workspace.  s3s_dstream_feed_batch (HOST addresses in d_comp / d_dst) stages
- *          the windows and the destinations of ALL entries there - the sum of comp_len + dst_capacity is the caller's memory
- *          bound - uploads, calls the device form and downloads out_len bytes per entry; it does not overlap the upload with
- *          the decode.
- * Not here the JNI natives and the Scala reader, a reader in the C++ host mirror, batching of Zstandard and encrypted streams,
- *          the map side (s3s_cstream_*). */
+ *          n == 1, S3S_CODEC_NONE (plain or encrypted), any stream of s3s_dstream_open_zstd.
+ * Key 17   S3S_OPT_DSTREAM_BATCH_ENTRIES (read-only) holds the number of entries of the context's last call that the batched path
+ *          answered: 0 after a call that went one by one or was refused; entries the single feed answered inside a batched call
+ *          (a sticky error, refused arguments, an empty window, a stale key, a feed repeated after a bad decode status) are not
+ *          counted.
+ * Memory   the device form works in the context's workspace; encrypted windows add one plain buffer per window there (the sum
+ *          of the windows' plain bytes + 320 bytes per window).  s3s_dstream_feed_batch (HOST addresses in d_comp / d_dst)
+ *          stages the windows and the destinations of ALL entries there - the sum of comp_len + dst_capacity is the caller's
+ *          memory bound - uploads, calls the device form and downloads out_len bytes per entry; it does not overlap the upload
+ *          with the decode.
+ * Not here the JNI natives and the Scala reader, a reader in the C++ host mirror, batching of Zstandard streams and of
+ *          S3S_CODEC_NONE, the map side (s3s_cstream_*). */
 typedef struct s3s_dstream_feed_entry {
   s3s_dstream* stream;        /* in */
   const uint8_t* d_comp;      /* in: this stream's window, starts at s3s_dstream_position(stream) */

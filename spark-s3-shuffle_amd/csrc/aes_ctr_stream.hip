@@ -12,6 +12,9 @@
 //
 // The IVs that start (whole) in the window are gathered into d_iv_out[16 p ..]: the host copies them with the feed's first
 // wait and keeps the one of the partition the feed leaves open.
+//
+// The kernel's body is aes_ctr_window_tile.inc: aes_ctr_stream_batch.hip runs the same statements over the windows of a batched
+// feed, in a translation unit of its own.
 #define S3S_AES_DEVICE
 #include "aes_ctr_stream_core.h"
 #include "s3s_internal.h"
@@ -37,56 +40,9 @@ __global__ __launch_bounds__(kWinThreads) void aes_ctr_window_kernel(const AesKe
                                                                      uint8_t* __restrict__ out, const int64_t* __restrict__ E,
                                                                      const int64_t* __restrict__ Q, uint8_t* __restrict__ iv_out, int32_t n,
                                                                      int64_t front, int64_t L) {
-  const int64_t tile0 = s3s_aes::win_chunk_start((int64_t)blockIdx.x * kWinTileChunks, front);
-  if (tile0 >= L) return;  // the whole workgroup
-  const int64_t tile_end = tile0 + kWinTile < L ? tile0 + kWinTile : L;
-  const LaneSbox sbox{s3s_aes::sbox_word(threadIdx.x & 63u)};
-  const int32_t p_lo = s3s_aes::win_last_start_le(E, 0, n - 1, tile0), p_hi = s3s_aes::win_last_start_le(E, p_lo, n - 1, tile_end - 1);
-
-  for (int k = 0; k < kWinChunks; k++) {
-    const int64_t x0 = tile0 + 16 * ((int64_t)threadIdx.x + (int64_t)kWinThreads * k);
-    const bool live = x0 < tile_end;
-    const int64_t lim = x0 + 16 < tile_end ? x0 + 16 : tile_end;
-    s3s_aes::WinCursor c;
-    s3s_aes::win_open(c, E, s3s_aes::win_last_start_le(E, p_lo, p_hi, x0), front, x0);
-    for (;;) {
-      s3s_aes::WinUnit u;
-      const bool has = s3s_aes::win_next(c, E, n, L, lim, live, u);
-      if (__builtin_amdgcn_ballot_w64(has) == 0) break;  // wave-uniform: every lane stays for the block encryption
-      const bool carried = u.part == 0 && front > 0;      // piece 0's IV came by in an earlier feed
-      const bool work = has && u.len > 0;
-      uint32_t ivw[4] = {iv0.w[0], iv0.w[1], iv0.w[2], iv0.w[3]};
-      const uint8_t* ivp = in + (carried ? 0 : E[u.part]);
-      if (work && !carried) {
-        __builtin_memcpy(ivw, ivp, 16);
-#pragma unroll
-        for (int w = 0; w < 4; w++) ivw[w] = __builtin_bswap32(ivw[w]);
-      }
-      uint32_t ks[4];
-      s3s_aes::keystream_block(keys.rk, NR, ivw, (uint64_t)u.block, ks, sbox);
-      if (work) {
-        if (u.is_iv) {  // whole (len 16): gathered for the host, dropped from the plain bytes
-          uint8_t* d = iv_out + 16 * (int64_t)u.part;
-          for (int i = 0; i < 16; i++) d[i] = ivp[i];
-        } else {
-          const uint8_t* s = in + (u.start + u.skip);
-          uint8_t* d = out + (Q[u.part] - (carried ? front - 16 : 0) + u.plain);
-          if (u.len == 16) {
-            uint32_t v[4];
-            __builtin_memcpy(v, s, 16);
-#pragma unroll
-            for (int w = 0; w < 4; w++) v[w] ^= __builtin_bswap32(ks[w]);
-            __builtin_memcpy(d, v, 16);
-          } else {
-            for (int i = 0; i < u.len; i++) {
-              const int b = u.skip + i;
-              d[i] = (uint8_t)(s[i] ^ (ks[b >> 2] >> (24 - 8 * (b & 3))));
-            }
-          }
-        }
-      }
-    }
-  }
+#define S3S_WIN_TILE blockIdx.x
+#include "aes_ctr_window_tile.inc"
+#undef S3S_WIN_TILE
 }
 
 }  // namespace

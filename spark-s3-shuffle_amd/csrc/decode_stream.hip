@@ -27,7 +27,8 @@
 // The host's RULES - the pieces of a window, the plain side, whether a kernel's words can be true, the verdicts, the open
 // partition's carry, the commit - are decode_stream_core.h (namespace s3s_ds; no HIP, tested on the CPU).  This file holds
 // what needs the context: staging, launches, waits, the sticky state and the error texts.  s3s_dstream_feed_device is the
-// list of a feed's phases; s3s_dstream_feed_batch_device runs the same rules per window around launches made once per call.
+// list of a feed's phases; s3s_dstream_feed_batch_device runs the same rules per window around launches made once per call,
+// the decrypt pass of encrypted windows included (aes_ctr_stream_batch.hip).
 #include <algorithm>
 #include <atomic>
 #include <new>
@@ -723,8 +724,13 @@ int s3s_dstream_feed(s3s_dstream* s, const uint8_t* comp, int64_t comp_len, uint
 }  // extern "C"
 
 // ---- the batched feed: one window of each of several streams per call ----------------------------------------------------
-// The path of s3s_dstream_feed_device for plain LZ4 / Snappy / LZF streams with every kernel launched once per CALL
-// (decode_stream_batch.hip) and the same three host waits whatever n is: checksums + discovery, frame tables + cut, decode.
+// The path of s3s_dstream_feed_device for LZ4 / Snappy / LZF streams, plain or encrypted, with every kernel launched once per
+// CALL (decode_stream_batch.hip) and the same three host waits whatever n is: checksums + discovery, frame tables + cut, decode.
+// Under IO encryption a window has the two sides of the single feed: the STORED side - the entry's d_comp, what the checksums
+// run over and what consumed, need_comp and the position count - and the PLAIN side, a slice of the crypt workspace that one
+// launch of the window pass (aes_ctr_stream_batch.hip) fills for all windows in front of discovery.  Discovery, the cut and the
+// decoders get the plain side through the same descriptors and do not know of the layer; ds::plain_side, ds::back_to_stored
+// and ds::commit map between the two, per window, exactly as feed_layout, feed_verdict and feed_commit do.
 // Every verdict is made on the host by the single feed's rules (decode_stream_core.h) from the same device words, and NO
 // stream's state is committed before the decode's verdict is known: when the batch's one decode status word comes back
 // non-zero, the undecided entries go through the single feed one by one, which says whose it was - nothing was committed, so
@@ -742,24 +748,32 @@ struct BatchWin {         // one entry that takes part in the batched path
   int32_t q = 0;
   int64_t carry = 0;
   int32_t second = -1;    // its task in the second checksum launch (the cut ended the feed inside a piece), or -1
+  ds::Plain pl;           // its plain side (without the layer: the stored side); q / c point into the arena
+  int32_t aes_tiles = 0;  // encrypted: tiles of the decrypt launch it owns
+  size_t plain_at = 0;    //            its plain buffer in B_CRYPT
 };
 
 // One arena, host (pinned) and device, uploaded in one copy:
-//   [offsets P + m][seeds P][seg_start P + m][piece -> window P][tile -> window T][tails m][windows: LzRange m][StreamWin m]
+//   [offsets P + m][seeds P][seg_start P + m][piece -> window P][tile -> window T]
+//   [encrypted: plain offsets P + m | AesWindow m | decrypt tile -> window TA][tails m][windows: LzRange m][StreamWin m]
 //   [second checksum launch: offsets 2 m | seeds m | seg_start 2 m | piece -> task m | tails m]
-// and behind it on the host the downloads: [status words m + 1][result words kWinWords x m][sums P][second sums m]
+// and behind it on the host the downloads: [status words m + 1][result words kWinWords x m][encrypted: gathered IVs 16 x P]
+// [sums P][second sums m], and what only the host reads: [encrypted: first cipher byte of every plain piece P + m].
+// The plain offsets of a window stand where its stored ones do (at its first piece + its index; m + 1 of its n + 1 slots are
+// used), so the piece -> window map serves both tables.  Without the layer the encrypted parts are empty
 struct BatchArena {
-  size_t off = 0, seed, seg, pw, tw, tail, rng, win, off2, seed2, seg2, pw2, tail2, total;
-  size_t st, res, sum, sum2, stage_total;
+  size_t off = 0, seed, seg, pw, tw, q, aw, atw, tail, rng, win, off2, seed2, seg2, pw2, tail2, total;
+  size_t st, res, iv, sum, sum2, c, stage_total;
   uint8_t *hs = nullptr, *da = nullptr;
-  void lay_out(size_t P, size_t M, size_t T) {
-    const size_t PM = P + M;
+  void lay_out(size_t P, size_t M, size_t T, size_t TA, bool enc) {
+    const size_t PM = P + M, e = enc ? 1 : 0;
     seed = al16(off + 8 * PM), seg = al16(seed + 8 * (P + 1)), pw = al16(seg + 4 * PM), tw = al16(pw + 4 * (P + 1));
-    tail = al16(tw + 4 * (T + 1)), rng = al16(tail + sizeof(TaskTail) * M), win = al16(rng + sizeof(LzRange) * M);
+    q = al16(tw + 4 * (T + 1)), aw = al16(q + e * 8 * PM), atw = al16(aw + e * sizeof(AesWindow) * M);
+    tail = al16(atw + e * 4 * (TA + 1)), rng = al16(tail + sizeof(TaskTail) * M), win = al16(rng + sizeof(LzRange) * M);
     off2 = al16(win + sizeof(StreamWin) * M), seed2 = al16(off2 + 16 * M), seg2 = al16(seed2 + 8 * M), pw2 = al16(seg2 + 8 * M);
     tail2 = al16(pw2 + 4 * M), total = al16(tail2 + sizeof(TaskTail) * M);
-    st = al16(total), res = al16(st + 4 * (M + 1)), sum = al16(res + 8 * kWinWords * M), sum2 = al16(sum + 8 * (P + 1));
-    stage_total = al16(sum2 + 8 * M);
+    st = al16(total), res = al16(st + 4 * (M + 1)), iv = res + 8 * kWinWords * M, sum = al16(iv + e * 16 * P), sum2 = al16(sum + 8 * (P + 1));
+    c = al16(sum2 + 8 * M), stage_total = al16(c + e * 8 * PM);
   }
   template <class X> X* h(size_t o) const { return reinterpret_cast<X*>(hs + o); }
   template <class X> const X* d(size_t o) const { return reinterpret_cast<const X*>(da + o); }
@@ -774,6 +788,11 @@ struct Batch {
   int32_t m = 0;             // windows
   size_t P = 0, SG = 0;      // pieces and checksum segment slots of all windows
   int64_t T = 0;             // LZ4: tiles of all windows
+  bool enc = false;          // the windows are those of encrypted streams: they have a plain side of their own
+  int64_t TA = 0;            // encrypted: tiles of the decrypt launch
+  size_t crypt_bytes = 0;    //            the plain buffers of all windows
+  size_t iv_bytes = 0;       //            the gathered IVs (16 x P), behind the result words on both sides
+  std::vector<int64_t> tmp;  //            batch_windows' offsets of one window
   BatchArena A;
   std::vector<size_t> ws_off;  // discovery workspace per window
   size_t st_bytes = 0, res_bytes = 0;
@@ -786,6 +805,9 @@ struct Batch {
   s3s_dstream_feed_entry& entry(const BatchWin& w) const { return E[w.e]; }
   int64_t* off_of(size_t wi) const { return A.h<int64_t>(A.off) + W[wi].piece0 + wi; }  // the window's n + 1 piece offsets
   int64_t* sums_of(const BatchWin& w) const { return A.h<int64_t>(A.sum) + w.piece0; }
+  int64_t* q_of(size_t wi) const { return A.h<int64_t>(A.q) + W[wi].piece0 + wi; }          // encrypted: its plain piece offsets
+  int64_t* c_of(size_t wi) const { return A.h<int64_t>(A.c) + W[wi].piece0 + wi; }          //            ... first cipher bytes
+  const uint8_t* ivs_of(const BatchWin& w) const { return A.h<uint8_t>(A.iv) + 16 * w.piece0; }  //        ... gathered IVs
   const int64_t* words_of(size_t wi) const { return A.h<int64_t>(A.res) + (size_t)kWinWords * wi; }  // (status and result words come down in one copy)
   int32_t status_of(size_t wi) const { return A.h<int32_t>(A.st)[wi]; }
 
@@ -809,10 +831,11 @@ struct Batch {
   }
 };
 
-// call-level refusals: nothing has been touched.  *plain: the batched path takes these streams
-int batch_check(Batch& b, bool* plain) {
+// call-level refusals: nothing has been touched.  *batched: the batched path takes these streams (which of them the context's
+// key setting lets run is an entry's matter: batch_windows)
+int batch_check(Batch& b, bool* batched) {
   s3s_ctx* ctx = b.ctx;
-  *plain = b.n_entries > 1 && !enc_on(ctx);
+  *batched = b.n_entries > 1;
   std::vector<const s3s_dstream*> seen;
   seen.reserve((size_t)b.n_entries);
   for (int32_t i = 0; i < b.n_entries; i++) {
@@ -821,7 +844,7 @@ int batch_check(Batch& b, bool* plain) {
     if (s->ctx != ctx) return fail(ctx, S3S_E_INVALID, "entry %d: the stream was opened on another context", i);
     if (s->codec != b.E[0].stream->codec || s->algo != b.E[0].stream->algo)
       return fail(ctx, S3S_E_INVALID, "entry %d: the streams of a batch must share codec and checksum algorithm", i);
-    if (s->enc || s->wlog != 0 || s->codec == S3S_CODEC_NONE) *plain = false;
+    if (s->wlog != 0 || s->codec == S3S_CODEC_NONE) *batched = false;
     seen.push_back(s);
   }
   std::sort(seen.begin(), seen.end());
@@ -830,25 +853,42 @@ int batch_check(Batch& b, bool* plain) {
 }
 
 // entries the single feed answers without device work keep its answer: a sticky error, an argument it refuses, an empty
-// window.  The others are the windows of the batch
+// window, a stream that the context's key setting leaves no feed (an encrypted one bound to an earlier setting, a plain one
+// under the layer).  The others are the windows of the batch: all plain, or all encrypted under the current key
 void batch_windows(Batch& b) {
+  s3s_ctx* ctx = b.ctx;
+  b.enc = enc_on(ctx);
   b.W.reserve((size_t)b.n_entries);
   for (int32_t i = 0; i < b.n_entries; i++) {
     s3s_dstream_feed_entry& e = b.E[i];
     const s3s_dstream* s = e.stream;
     const int64_t left = s->off[(size_t)s->nparts] - s->at.pos;
-    if (s->err != S3S_OK || e.comp_len <= 0 || e.dst_capacity < 0 || !e.d_comp || (e.dst_capacity > 0 && !e.d_dst) || e.comp_len > left) {
+    const bool no_feed = s->enc ? (s->epoch != ctx->enc_epoch || !b.enc) : b.enc;  // feed_check's two refusals
+    if (s->err != S3S_OK || e.comp_len <= 0 || e.dst_capacity < 0 || !e.d_comp || (e.dst_capacity > 0 && !e.d_dst) || e.comp_len > left || no_feed) {
       b.single(e);
       continue;
     }
+    const ds::Range R = range_of(s);
     BatchWin w;
     w.e = i;
-    w.n = ds::piece_count(range_of(s), s->at, e.comp_len);
+    w.n = ds::piece_count(R, s->at, e.comp_len);
     w.piece0 = b.P;
     w.seg0 = b.SG;
     b.P += (size_t)w.n;
-    b.SG += (size_t)ds::window_segs(range_of(s), s->at, e.comp_len, w.n, kChecksumSegBytes);
-    if (b.codec == S3S_CODEC_LZ4) b.T += lz4_tile_count(e.comp_len);
+    b.SG += (size_t)ds::window_segs(R, s->at, e.comp_len, w.n, kChecksumSegBytes);
+    int64_t PL = e.comp_len;
+    if (b.enc) {  // what the plain side needs of the workspace; batch_layout builds it again, in the arena
+      const size_t n1 = (size_t)w.n + 1;
+      b.tmp.assign(3 * n1, 0);
+      for (int32_t p = 0; p < w.n; p++) ds::piece(R, s->at, e.comp_len, p, b.tmp[(size_t)p], b.tmp[(size_t)p + 1]);
+      const ds::Plain pl = ds::plain_side(R, s->at, e.comp_len, w.n, b.tmp.data(), b.tmp.data() + n1, b.tmp.data() + 2 * n1);
+      PL = pl.PL;
+      w.aes_tiles = aes_ctr_window_tiles(pl.m, pl.front, b.tmp[(size_t)pl.m]);
+      w.plain_at = b.crypt_bytes;
+      b.TA += w.aes_tiles;
+      b.crypt_bytes += ((size_t)PL + 64 + 255) & ~size_t(255);  // PL + 64 bytes as the single feed's, every buffer aligned as B_CRYPT is
+    }
+    if (b.codec == S3S_CODEC_LZ4) b.T += lz4_tile_count(PL);
     b.W.push_back(w);
   }
   b.m = (int32_t)b.W.size();
@@ -860,12 +900,13 @@ int batch_layout(Batch& b) {
   BatchArena& A = b.A;
   const size_t M = (size_t)b.m, P = b.P, SG = b.SG;
   const int codec = b.codec;
-  A.lay_out(P, M, (size_t)b.T);
+  A.lay_out(P, M, (size_t)b.T, (size_t)b.TA, b.enc);
   int rc;
   if ((rc = ensure_stage(ctx, A.stage_total))) return rc;
   if ((rc = ensure(ctx, B_PLAN, A.total))) return rc;
-  b.st_bytes = al16(4 * (M + 1)), b.res_bytes = 8 * kWinWords * M;
-  if ((rc = ensure(ctx, B_STATUS, b.st_bytes + b.res_bytes + 16))) return rc;
+  b.st_bytes = al16(4 * (M + 1)), b.res_bytes = 8 * kWinWords * M, b.iv_bytes = b.enc ? 16 * P : 0;
+  if ((rc = ensure(ctx, B_STATUS, b.st_bytes + b.res_bytes + b.iv_bytes + 16))) return rc;  // [status words][result words][gathered IVs]
+  if (b.enc && (rc = ensure(ctx, B_CRYPT, b.crypt_bytes + 64))) return rc;
   if ((rc = ensure(ctx, B_SUMS, 8 * (P + M + 1)))) return rc;
   if ((rc = ensure(ctx, B_PARTIAL, 16 * (SG > 0 ? SG : 1)))) return rc;
   // discovery workspace per window: LZ4 4 x (tiles + 1) int64 + (tiles + 1) int32; Snappy / LZF (n + 1) int32 + (n + 2) int64
@@ -873,6 +914,7 @@ int batch_layout(Batch& b) {
   size_t ws = 0;
   for (size_t i = 0; i < M; i++) {
     b.ws_off[i] = ws;
+    // (the tiles of the stored window bound those of its plain side: a slot too many, never one too few)
     const size_t c1 = codec == S3S_CODEC_LZ4 ? (size_t)lz4_tile_count(b.entry(b.W[i]).comp_len) + 1 : (size_t)b.W[i].n + 2;
     ws += al16(4 * 8 * c1 + 4 * c1);
   }
@@ -885,7 +927,7 @@ int batch_layout(Batch& b) {
   b.d_sums = dev<int64_t>(ctx, B_SUMS);
 
   memset(A.hs + A.tail, 0, A.off2 - A.tail);
-  int32_t tile0 = 0;
+  int32_t tile0 = 0, aes_tile0 = 0;
   for (int32_t wi = 0; wi < b.m; wi++) {
     BatchWin& w = b.W[(size_t)wi];
     const s3s_dstream_feed_entry& e = b.entry(w);
@@ -903,12 +945,32 @@ int batch_layout(Batch& b) {
     t.n_segs = (int32_t)segs;
     t.data = e.d_comp;
     t.data_len = L;
+    // the plain side: what discovery, the cut and the decoders see.  Without the layer it is the stored side
+    ds::Plain& pl = w.pl = ds::plain_side(R, s->at, L, w.n, b.off_of((size_t)wi), b.enc ? b.q_of((size_t)wi) : nullptr, b.enc ? b.c_of((size_t)wi) : nullptr);
+    const uint8_t* comp = e.d_comp;
+    if (b.enc) {
+      uint8_t* plain = dev<uint8_t>(ctx, B_CRYPT) + w.plain_at;
+      comp = plain;
+      AesWindow& a = A.h<AesWindow>(A.aw)[wi];
+      a.in = e.d_comp;
+      a.out = plain;
+      a.E = A.d<int64_t>(A.off) + o0;
+      a.Q = A.d<int64_t>(A.q) + o0;
+      a.iv_out = reinterpret_cast<uint8_t*>(b.d_result) + b.res_bytes + 16 * w.piece0;
+      a.m = pl.m;
+      a.tile0 = aes_tile0;
+      a.front = pl.front;
+      a.L = b.off_of((size_t)wi)[pl.m];
+      a.iv = {{s3s_aes::load_be32(s->iv), s3s_aes::load_be32(s->iv + 4), s3s_aes::load_be32(s->iv + 8), s3s_aes::load_be32(s->iv + 12)}};
+      for (int32_t t2 = 0; t2 < w.aes_tiles; t2++) A.h<int32_t>(A.atw)[aes_tile0 + t2] = wi;
+      aes_tile0 += w.aes_tiles;
+    }
     LzRange& r = A.h<LzRange>(A.rng)[wi];
     uint8_t* ws_i = dev<uint8_t>(ctx, B_PART_NFRAMES) + b.ws_off[(size_t)wi];
-    const int32_t nt = codec == S3S_CODEC_LZ4 ? lz4_tile_count(L) : 0;
+    const int32_t nt = codec == S3S_CODEC_LZ4 ? lz4_tile_count(pl.PL) : 0;
     const size_t c1 = codec == S3S_CODEC_LZ4 ? (size_t)nt + 1 : (size_t)w.n + 2;
-    r.comp = e.d_comp;
-    r.comp_len = L;
+    r.comp = comp;
+    r.comp_len = pl.PL;
     r.n_tiles = nt;
     r.tile0 = tile0;
     r.spec_entry = reinterpret_cast<int64_t*>(ws_i);
@@ -922,12 +984,11 @@ int batch_layout(Batch& b) {
     r.dst_capacity = e.dst_capacity;
     for (int32_t t2 = 0; t2 < nt; t2++) A.h<int32_t>(A.tw)[tile0 + t2] = wi;
     tile0 += nt;
-    const ds::Plain pl = ds::plain_side(R, s->at, L, w.n, b.off_of((size_t)wi), nullptr, nullptr);  // (no layer: only the three numbers below)
     StreamWin& x = A.h<StreamWin>(A.win)[wi];
     x.range_left = pl.pleft;
     x.last_pend = pl.plast_pend;
     x.first_piece = (int32_t)w.piece0;
-    x.n_pieces = w.n;
+    x.n_pieces = pl.m;
     x.first_mid = pl.first_mid ? 1 : 0;
   }
   return S3S_OK;
@@ -942,6 +1003,11 @@ int batch_discover(Batch& b) {
   HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, b.st_bytes + b.res_bytes, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(A.da, A.hs, A.off2, hipMemcpyHostToDevice, ctx->stream));
   record(ctx, 0);
+  if (b.enc) {  // in front of discovery: every window's plain side and its IVs, one launch
+    launch_aes_ctr_window_batch(ctx->enc_keys, ctx->enc_rounds, A.d<AesWindow>(A.aw), A.d<int32_t>(A.atw), (int32_t)b.TA, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  const int64_t* d_poff = A.d<int64_t>(b.enc ? A.q : A.off);  // the pieces discovery walks
   if (b.algo != S3S_CHECKSUM_NONE) {
     launch_checksum_batch(b.algo, A.d<TaskTail>(A.tail), b.m, (int32_t)b.SG, (int32_t)b.P, A.d<int64_t>(A.off), A.d<int32_t>(A.seg),
                           ctx->buf[B_TABLES].p, dev<uint32_t>(ctx, B_PARTIAL), b.d_sums, ctx->stream);
@@ -955,10 +1021,10 @@ int batch_discover(Batch& b) {
     launch_lz4_speculate_batch(d_rng, A.d<int32_t>(A.tw), (int32_t)b.T, ctx->stream);
     launch_lz4_resolve_stream_batch(d_rng, d_win, b.m, ctx->stream);
   } else {
-    launch_snappy_count_stream_batch(d_rng, d_win, b.m, A.d<int64_t>(A.off), A.d<int32_t>(A.pw), (int32_t)b.P, b.cf, ctx->stream);
+    launch_snappy_count_stream_batch(d_rng, d_win, b.m, d_poff, A.d<int32_t>(A.pw), (int32_t)b.P, b.cf, ctx->stream);
   }
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(A.h<int32_t>(A.st), b.d_status, b.st_bytes + b.res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(A.h<int32_t>(A.st), b.d_status, b.st_bytes + b.res_bytes + b.iv_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // the single feed's verdicts, per window, from the same words
   for (int32_t wi = 0; wi < b.m; wi++) {
@@ -967,6 +1033,7 @@ int batch_discover(Batch& b) {
     memset(&e.result, 0, sizeof e.result);
     e.result.bad_partition = -1;
     w.first_frame = b.total_frames;
+    if (w.pl.PL == 0) continue;  // no plain byte (IVs, whole or cut, and nothing else): nothing was discovered, as in feed_discover
     if (b.status_of((size_t)wi) != 0) {
       b.refused(w, b.status_of((size_t)wi), b.codec == S3S_CODEC_LZ4 ? "frame chain" : "chunk chain");
       continue;
@@ -975,7 +1042,7 @@ int batch_discover(Batch& b) {
     w.stop = res[0];
     w.need_comp = res[1];
     w.n_frames = res[2];
-    if (!ds::stop_valid(w.stop, w.need_comp, e.comp_len) || w.n_frames < 0) {
+    if (!ds::stop_valid(w.stop, w.need_comp, w.pl.PL) || w.n_frames < 0) {
       b.decide(w, bad_stop(ctx, "frame"));
       w.n_frames = 0;
       continue;
@@ -1021,7 +1088,7 @@ int batch_cut(Batch& b) {
   }
   HIP_TRY(ctx, hipMemcpyAsync(A.da + A.rng, A.hs + A.rng, A.off2 - A.rng, hipMemcpyHostToDevice, ctx->stream));
   if (b.codec == S3S_CODEC_LZ4) launch_lz4_emit_batch(d_rng, A.d<int32_t>(A.tw), (int32_t)b.T, ctx->stream);
-  else launch_snappy_emit_stream_batch(d_rng, d_win, b.m, A.d<int64_t>(A.off), A.d<int32_t>(A.pw), (int32_t)b.P, b.cf, ctx->stream);
+  else launch_snappy_emit_stream_batch(d_rng, d_win, b.m, A.d<int64_t>(b.enc ? A.q : A.off), A.d<int32_t>(A.pw), (int32_t)b.P, b.cf, ctx->stream);
   launch_frames_cut_batch(b.codec, d_rng, d_win, b.m, ctx->stream);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(A.h<int32_t>(A.st), b.d_status, b.st_bytes + b.res_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1054,11 +1121,18 @@ void batch_verdicts(Batch& b) {
         b.decide(w, bad_cut(ctx, "frame"));
         continue;
       }
-      if (w.consumed == 0) {
+      if (ds::nothing_fits(w.pl, w.consumed)) {
         b.decide(w, no_room(ctx, &e.result, e.dst_capacity, res[7], "unit"));
         continue;
       }
     }
+    const ds::Stored st = ds::back_to_stored(w.pl, w.consumed, w.need_comp);  // consumed and need_comp were plain offsets so far
+    if (st.into_short_part) {
+      b.refused(w, S3S_E_BAD_FRAME, "partition shorter than its IV");
+      continue;
+    }
+    w.consumed = st.consumed;
+    w.need_comp = st.need_comp;
     const ds::Verdict v = ds::verdict(R, s->at, w.consumed, b.sums_of(w));
     if (v.bad >= 0) {
       b.decide(w, stick(s, &e.result, S3S_E_CHECKSUM, v.bad, ""));
@@ -1140,7 +1214,8 @@ void batch_commit(Batch& b) {
     if (w.decided) continue;
     s3s_dstream_feed_entry& e = b.entry(w);
     const int64_t carry = w.second >= 0 ? b.A.h<int64_t>(b.A.sum2)[w.second] : w.carry;
-    const ds::Commit c = ds::commit(range_of(e.stream), e.stream->at, 0, w.q, w.consumed, carry, w.need_comp);
+    const ds::Commit c = ds::commit(range_of(e.stream), e.stream->at, w.pl.front, w.q, w.consumed, carry, w.need_comp);
+    if (c.iv_piece >= 0) memcpy(e.stream->iv, b.ivs_of(w) + 16 * (size_t)c.iv_piece, sizeof e.stream->iv);  // the open partition's IV: it started in this window
     e.result.consumed = w.consumed;
     e.result.out_len = w.out_len;
     e.result.need_comp = c.need_comp;
@@ -1157,13 +1232,14 @@ int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* E, int32
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   if (n_entries < 0 || (n_entries > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  ctx->dstream_batch_entries = 0;  // S3S_OPT_DSTREAM_BATCH_ENTRIES: set where the batched path has answered
   BatchVerdict<s3s_dstream_feed_entry> verdict(E, n_entries);
   if (n_entries == 0) return verdict.finish(S3S_OK);
   Batch b = {ctx, E, n_entries};
-  bool plain;
+  bool batched;
   int rc;
-  if ((rc = batch_check(b, &plain))) return rc;
-  if (!plain) {  // nothing to batch: one by one, in order
+  if ((rc = batch_check(b, &batched))) return rc;
+  if (!batched) {  // nothing to batch: one by one, in order
     for (int32_t i = 0; i < n_entries; i++) b.single(E[i]);
     return verdict.finish(b.first_error());
   }
@@ -1172,11 +1248,26 @@ int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* E, int32
   b.cf = b.codec == S3S_CODEC_LZF ? kChunkLzf : kChunkSnappy;
   batch_windows(b);
   if (b.m == 0) return verdict.finish(b.first_error());
-  if (b.P > (size_t)ds::kMaxCount || b.SG > (size_t)ds::kMaxCount || b.T > ds::kMaxCount) return fail(ctx, S3S_E_UNSUPPORTED, "batch too large for one call");
+  if (b.P > (size_t)ds::kMaxCount || b.SG > (size_t)ds::kMaxCount || b.T > ds::kMaxCount || b.TA > ds::kMaxCount)
+    return fail(ctx, S3S_E_UNSUPPORTED, "batch too large for one call");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (auto& v : ctx->stage_ms) v = 0;
   if ((rc = batch_layout(b))) return rc;
-  if ((rc = batch_discover(b))) return rc;                      // wait 1: checksums + discovery
+  // the host copies of IVs the arena holds - the carried ones in the descriptors, the gathered ones - go with the call, as a
+  // stream's own copy goes with the stream; before a single feed lays the staging area out anew
+  struct WipeIvs {
+    Batch& b;
+    bool done = false;
+    void now() {
+      if (b.enc && !done) {
+        wipe(b.A.hs + b.A.aw, b.A.atw - b.A.aw);
+        wipe(b.A.hs + b.A.iv, b.iv_bytes);
+      }
+      done = true;
+    }
+    ~WipeIvs() { now(); }
+  } wipe_ivs{b};
+  if ((rc = batch_discover(b))) return rc;                      // wait 1: decrypt + checksums + discovery
   if (b.total_frames > 0 && (rc = batch_cut(b))) return rc;     // wait 2: frame tables + cut
   batch_verdicts(b);
   if (b.any_decode || b.n_second > 0) {
@@ -1188,17 +1279,21 @@ int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* E, int32
       std::vector<int32_t> todo;
       for (const BatchWin& w : b.W)
         if (!w.decided) todo.push_back(w.e);
+      ctx->dstream_batch_entries = b.m - (int32_t)todo.size();  // what the batch decided itself
+      wipe_ivs.now();
       for (int32_t i : todo) b.single(E[i]);
       return verdict.finish(b.first_error());
     }
   }
   batch_commit(b);
+  ctx->dstream_batch_entries = b.m;
   return verdict.finish(b.first_error());
 }
 
 int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* E, int32_t n_entries) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
+  ctx->dstream_batch_entries = 0;
   if (n_entries < 0 || (n_entries > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
   BatchVerdict<s3s_dstream_feed_entry> verdict(E, n_entries);
   if (n_entries == 0) return verdict.finish(S3S_OK);

@@ -138,6 +138,23 @@ struct AesWindowIv {
 void launch_aes_ctr_window(const AesKeys& keys, int rounds, const AesWindowIv& iv0, const uint8_t* d_in, uint8_t* d_out,
                            const int64_t* d_stored_off, const int64_t* d_plain_off, uint8_t* d_iv_out, int32_t n_pieces, int64_t front,
                            int64_t window_len, hipStream_t st);
+// The window form over the windows of a batched feed, one launch: window i is d_wins[i] (what launch_aes_ctr_window takes as
+// arguments, in device memory; tile0 = its first tile in the launch), tile t of the launch belongs to window d_tile_win[t].
+// aes_ctr_window_tiles is the number of tiles a window owns (0 without a plain piece or a stored byte).  The carried IV of a
+// window is in its descriptor (an IV is stored in the clear in the stream); the round keys are kernel arguments as everywhere.
+struct AesWindow {
+  const uint8_t* in;   // the stored window
+  uint8_t* out;        // its plain bytes
+  const int64_t* E;    // m + 1 stored piece offsets, window-relative
+  const int64_t* Q;    // m + 1 plain piece offsets
+  uint8_t* iv_out;     // 16 x m
+  int32_t m, tile0;
+  int64_t front, L;    // L = E[m]
+  AesWindowIv iv;      // the carried IV (front > 0)
+};
+int32_t aes_ctr_window_tiles(int32_t n_pieces, int64_t front, int64_t window_len);
+void launch_aes_ctr_window_batch(const AesKeys& keys, int rounds, const AesWindow* d_wins, const int32_t* d_tile_win, int32_t total_tiles,
+                                 hipStream_t st);
 // The map-side stream's form (aes_ctr_cstream.hip; the same arithmetic): the output d_dst[0, out_len) of one feed -> IV | cipher
 // text.  d_piece_off[n_pieces + 1] are the stored piece offsets of the output ([0] = 0, [n_pieces] = out_len, pieces behind the
 // cut empty), d_ivs one IV per piece (entry 0: the open partition's carried IV when `front` > 0 stored bytes of it lie in front

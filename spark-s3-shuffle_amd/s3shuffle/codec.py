@@ -28,6 +28,7 @@ OPT_ZSTD_DECODE_VARIANT = 13  # ABI 11, additive: 1 (default) = block-independen
 OPT_ZSTD_DECODE_BLOCKS = 14  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the block path
 OPT_ZSTD_DECODE_STAGED = 15  # ABI 11, additive: 0 (default) / 1 = Zstandard frames with history across blocks decode in stages (entropy per block, copies per frame)
 OPT_ZSTD_DECODE_STAGED_BLOCKS = 16  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the staged path
+OPT_DSTREAM_BATCH_ENTRIES = 17  # ABI 11, additive, read-only: entries of the last feed_streams* call that the batched path answered (0: it went one by one)
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
 STATUS_NOT_RUN = -100  # per-entry status of a batch call that failed as a call before this entry had a verdict (ABI 6)
@@ -297,6 +298,11 @@ class Codec:
     def zstd_decode_staged_blocks(self) -> int:
         """Blocks of the last Zstandard decode call whose frames completed on the staged path (OPT_ZSTD_DECODE_STAGED = 1), else 0."""
         return self.get_option(OPT_ZSTD_DECODE_STAGED_BLOCKS)
+
+    @property
+    def batch_entries(self) -> int:
+        """Entries of the last feed_streams* call that the batched path answered; 0 when the call went one by one or was refused."""
+        return self.get_option(OPT_DSTREAM_BATCH_ENTRIES)
 
     def stage_ms(self, stage: int) -> float:
         return float(self._lib.s3s_stage_ms(self._h, stage))
