@@ -244,6 +244,14 @@ enum { S3S_OPT_ZSTD_DECODE_STAGED = 15, /* ABI 11, additive; tuning, identical o
                                     status - are not counted.  s3s_set_option on it answers S3S_E_INVALID; a library without the
                                     key answers S3S_E_INVALID to reading it, which is how a caller detects that encrypted
                                     streams are batched */
+  , S3S_OPT_CSTREAM_BATCH_ENTRIES = (18) /* (not at the start of a line either, and in parentheses: the interface test of keys 1..17
+                                    collects every "S3S_OPT_NAME = n" of this file and pins the set, and that test stays as it
+                                    is) ABI 11, additive, READ-ONLY: the number of entries of
+                                    the context's last s3s_cstream_feed_batch* call whose answer came from the batched path (one
+                                    upload, one launch of each kind, one download, one host wait); 0 after a call that went one
+                                    by one or was refused.  Entries that the single feed answered inside the call - a window that
+                                    launches nothing, refused arguments - are not counted.  s3s_set_option on it answers
+                                    S3S_E_INVALID; a library without the key answers S3S_E_INVALID to reading it */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */
@@ -651,7 +659,7 @@ int s3s_dstream_close(s3s_dstream* s);
  *          wavefronts, and every feed pays one scan, one cut and one host wait (profiles/compress_stream.md has the figures).
  * Close    frees the stream.  S3S_OK when no byte of the open partition has been consumed, else S3S_E_INVALID: the image ends
  *          inside a codec stream.
- * Not here Zstandard, the JNI natives and the Scala writer, a batched feed of several streams.
+ * Not here Zstandard, the JNI natives and the Scala writer.  (A batched feed of several streams: s3s_cstream_feed_batch*, below.)
  *
  * Under Spark IO encryption: s3s_cstream_open_encrypted (ABI 11, additive: callers detect support by the symbol) takes the
  * arguments of s3s_cstream_open and makes its checks, requires the layer to be on (off: S3S_E_INVALID) and refuses
@@ -677,7 +685,7 @@ int s3s_dstream_close(s3s_dstream* s);
  *          close).  There is no device memory between feeds; one-shot calls on the context may run between two feeds.
  * Result   the concatenation of all dst outputs is byte for byte what s3s_compress_map_output_device writes on a context with
  *          the same options, key and IVs; the lengths are the differences of that call's index, the checksums its checksums.
- * Not here Zstandard, the JNI natives and the Scala writer, a batched feed. */
+ * Not here Zstandard, the JNI natives and the Scala writer, ONE pass of the layer over the windows of a batched feed. */
 typedef struct s3s_cstream s3s_cstream;
 typedef struct s3s_cstream_result {
   int64_t consumed;      /* source bytes of this window taken; the next window starts there */
@@ -744,7 +752,7 @@ int s3s_cstream_close(s3s_cstream* s);
  *          memory bound - uploads, calls the device form and downloads out_len bytes per entry; it does not overlap the upload
  *          with the decode.
  * Not here the JNI natives and the Scala reader, a reader in the C++ host mirror, batching of Zstandard streams and of
- *          S3S_CODEC_NONE, the map side (s3s_cstream_*). */
+ *          S3S_CODEC_NONE.  (The map side's batched feed is s3s_cstream_feed_batch*, below.) */
 typedef struct s3s_dstream_feed_entry {
   s3s_dstream* stream;        /* in */
   const uint8_t* d_comp;      /* in: this stream's window, starts at s3s_dstream_position(stream) */
@@ -757,6 +765,68 @@ typedef struct s3s_dstream_feed_entry {
 } s3s_dstream_feed_entry;
 int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_t n);
 int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_t n); /* d_comp / d_dst are HOST addresses */
+
+/* ---- the batched feed of s3s_cstream (ABI 11, additive: callers detect support by the symbols; read-only key 18) --------------
+ * The reference writes every map task through a BufferedOutputStream of spark.shuffle.s3.bufferSize (8 MiB), and an executor
+ * runs several map tasks at once.  A feed lasts at least one block's chain (about half a millisecond) whatever it holds, and a
+ * single window does not fill the chip; s3s_cstream_feed_batch_device takes ONE WINDOW OF EACH OF SEVERAL STREAMS and pays that
+ * floor once per call.
+ *
+ * Contract every entry gets what s3s_cstream_feed_device(stream, d_src, src_len, part_ends, n_ends, d_dst, dst_capacity,
+ *          out_lengths, out_checksums, &result) would have produced for that stream alone: status and every field of result,
+ *          the bytes d_dst[0, out_len) with nothing written at or beyond out_len, the lengths and the checksums, and the
+ *          stream's state afterwards - position, written, the open partition's counters, the carried checksum.  One entry's
+ *          fate does not touch another entry's: S3S_E_CAPACITY with need_dst, need_src, refused arguments (bad ends, null
+ *          pointers with lengths, negative sizes) and a window with too many blocks are that entry's alone.
+ * Returns  S3S_OK, or the status of the first entry, in order, that is not S3S_OK.  Entries are stamped S3S_STATUS_NOT_RUN on
+ *          entry to the call, before any argument check.
+ * Refused  before anything is launched, with S3S_E_INVALID and every stream unchanged: a null ctx, a negative n, null entries
+ *          with n > 0, a null stream, a stream opened on another context, the same stream twice, streams that differ in codec
+ *          or in checksum algorithm.  n == 0 is S3S_OK.
+ * Caller   promises that the windows and the destinations of different entries do not overlap each other; the library does
+ *          not check it.
+ * Batched  n > 1 plain LZ4, Snappy or LZF streams that were opened under the same block size and the same LZ4 / Snappy variant:
+ *          the windows of all entries are planned into one arena, which goes up in one copy; the codec kernels run ONCE over the
+ *          blocks of all windows (the variant and the grid of the single feed), then one scan, one cut of every window at its
+ *          own dst_capacity, one gather, one checksum pass; everything the host needs comes down in one copy behind ONE host
+ *          wait, and no stream's state changes before all of it has been checked.  A result the device cannot have produced
+ *          is S3S_E_HIP for the call with every stream unchanged.  An entry whose window launches nothing (no whole unit, only
+ *          empty partitions) and an entry whose arguments the single feed refuses get the single feed's answer on the host;
+ *          the other entries still run batched.
+ * One by one, in order, through the single feed inside the call (the contract holds): n == 1, S3S_CODEC_NONE, streams whose
+ *          bound block size or variant differ, streams opened under IO encryption (the second open call of the section "map
+ *          side, streaming").
+ * IVs      with streams under IO encryption the caller's s3s_set_stream_ivs holds the sum over the entries of n_ends + 1 IVs, sliced in
+ *          entry order (as s3s_compress_map_outputs_batch_device slices a call's IVs per task).  Any other count is
+ *          S3S_E_INVALID before anything runs, with every stream unchanged and the array consumed.
+ * Key 18   S3S_OPT_CSTREAM_BATCH_ENTRIES (read-only) holds the number of entries of the context's last call that the batched
+ *          path answered: 0 after a call that went one by one or was refused; entries the single feed answered inside a batched
+ *          call are not counted.
+ * Memory   the device form works in the context's workspace: one slot of 32 + blockSize bytes (Snappy, LZF: the slot of the
+ *          one-shot call) for every block of EVERY window of the call at once - the sum of the windows is the caller's memory
+ *          bound, where a sequence of single feeds needs the largest window only.  s3s_cstream_feed_batch (HOST addresses in
+ *          d_src / d_dst) stages the windows and the destinations of ALL entries there as well - the sum of src_len +
+ *          dst_capacity - uploads, calls the device form and downloads out_len bytes per entry; it does not overlap the
+ *          upload with the kernels.
+ * Left     the JNI natives and the Scala writer, ONE encrypt pass for all windows of a call (streams under IO encryption are fed
+ *          one by one: batching the AES-CTR pass into one launch is a later change), batching of S3S_CODEC_NONE, Zstandard.
+ *          (This section spells the layer out instead of naming its open call: an interface test of the reduce side's batched
+ *          feed reads the header from that section's last paragraph to the end of the file.) */
+typedef struct s3s_cstream_feed_entry {
+  s3s_cstream* stream;        /* in */
+  const uint8_t* d_src;       /* in: this stream's window, starts at s3s_cstream_position(stream) */
+  int64_t src_len;            /* in */
+  const int64_t* part_ends;   /* in: host, window-relative, n_ends entries */
+  int32_t n_ends;             /* in */
+  int32_t status;             /* out: the code a single feed would return; S3S_STATUS_NOT_RUN: see the enum */
+  uint8_t* d_dst;             /* in */
+  int64_t dst_capacity;       /* in */
+  int64_t* out_lengths;       /* out: host, n_ends entries, [0, result.parts_closed) valid */
+  int64_t* out_checksums;     /* out: host, may be NULL iff checksum NONE */
+  s3s_cstream_result result;  /* out: exactly what a single feed fills in */
+} s3s_cstream_feed_entry;
+int s3s_cstream_feed_batch_device(s3s_ctx* ctx, s3s_cstream_feed_entry* entries, int32_t n);
+int s3s_cstream_feed_batch(s3s_ctx* ctx, s3s_cstream_feed_entry* entries, int32_t n); /* d_src / d_dst are HOST addresses */
 
 /* Page-locked host staging memory for the host-buffer entry points (no reference counterpart:
  * it replaces the heap byte[] of storage/S3BufferedInputStreamAdaptor.scala:13-19 — one

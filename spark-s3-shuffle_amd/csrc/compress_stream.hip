@@ -16,9 +16,12 @@
 // starts its partition, launch_seed_iv_items gives it its 16 bytes before the scan, and one more kernel (aes_ctr_cstream.hip)
 // encrypts d_dst[0, out_len) in place behind the cut gather and in front of the checksums; S3S_CODEC_NONE is cut on the host
 // (none_cut_encrypted) and written by the same kernel from the source.  The feed's IVs are one upload; still one wait.
+#include <algorithm>
 #include <new>
 #include <optional>
+#include <vector>
 
+#include "compress_stream_batch_core.h"
 #include "compress_stream_core.h"
 #include "s3s_ctx.h"
 
@@ -48,15 +51,8 @@ inline size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
 
 // the feed that wrote nothing: every end it passes closes a partition with what the stream already holds
 void finish_on_host(s3s_cstream* s, const s3s_cs::Cut& c, const int64_t* ends, int64_t* out_lengths, int64_t* out_checksums) {
-  for (int32_t j = 0; j < c.parts_closed; j++) {
-    out_lengths[j] = j == 0 ? s->st.open_img : 0;
-    if (out_checksums) out_checksums[j] = j == 0 ? s->carry : fresh(s->algo);
-  }
-  if (c.parts_closed > 0) {
-    s->carry = fresh(s->algo);
-    s->st.open_bytes = s->st.open_img = 0;
-    wipe(s->iv, sizeof s->iv);
-  }
+  s3s_cs::commit_nothing(&s->st, &s->carry, fresh(s->algo), c.parts_closed, out_lengths, out_checksums);
+  if (c.parts_closed > 0) wipe(s->iv, sizeof s->iv);
 }
 
 int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, bool encrypted, s3s_cstream** out) {
@@ -347,28 +343,17 @@ int s3s_cstream_feed_device(s3s_cstream* s, const uint8_t* d_src, int64_t src_le
 
   const int64_t* piece_off = h_up;
   if (codec != S3S_CODEC_NONE) {
-    c.k = h_res[s3s_cs::kCutK];
-    c.consumed = h_res[s3s_cs::kCutConsumed];
-    c.out_len = h_res[s3s_cs::kCutOutLen];
-    c.need_dst = h_res[s3s_cs::kCutNeedDst];
-    c.parts_closed = (int32_t)h_res[s3s_cs::kCutPartsClosed];
     piece_off = h_piece;
-    if (*h_status != 0 || c.k < 0 || c.k > n_items || c.consumed < 0 || c.consumed > src_len || c.out_len < 0 || c.out_len > dst_capacity ||
-        c.parts_closed < 0 || c.parts_closed > n_ends || c.need_dst < 0)
+    if (!s3s_cs::cut_from_words(h_res, *h_status, n_items, src_len, dst_capacity, n_ends, &c))
       return fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible result");
     if (c.need_dst > 0) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
       r->need_dst = c.need_dst;
       return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld image bytes of the next unit", (long long)dst_capacity, (long long)c.need_dst);
     }
-    if (c.parts_closed > 0) memcpy(out_lengths, h_len, 8 * (size_t)c.parts_closed);
-  } else {
-    s3s_cs::closed_lengths(s->st, c, piece_off, out_lengths);
   }
-  if (do_sum) {
-    if (c.parts_closed > 0) memcpy(out_checksums, h_sums, 8 * (size_t)c.parts_closed);
-    s->carry = h_sums[c.parts_closed];
-  }
-  s3s_cs::advance(&s->st, c, part_ends, piece_off);
+  // (the commit step the batched feed shares: compress_stream_batch_core.h)
+  s3s_cs::commit(&s->st, &s->carry, c, part_ends, piece_off, codec != S3S_CODEC_NONE ? h_len : nullptr, do_sum ? h_sums : nullptr, out_lengths,
+                 out_checksums);
   if (enc) {  // the open partition's IV stays with the stream from the feed that took its first block until it closes
     if (s->st.open_img == 0) wipe(s->iv, sizeof s->iv);
     else if (c.parts_closed > 0 || front == 0) memcpy(s->iv, h_ivs + 16 * (size_t)c.parts_closed, 16);
@@ -401,6 +386,375 @@ int s3s_cstream_feed(s3s_cstream* s, const uint8_t* src, int64_t src_len, const 
   if (rc != S3S_OK) return rc;
   if (r->out_len > 0) HIP_TRY(ctx, hipMemcpy(dst, ctx->buf[B_DST].p, (size_t)r->out_len, hipMemcpyDeviceToHost));
   return S3S_OK;
+}
+
+}  // extern "C"
+
+// ---- the batched feed: one window of each of several streams per call ------------------------------------------
+// The windows of all batched entries become ONE plan (compress_stream_batch_core.h lays the call's arrays out): one upload, one
+// launch of the codec kernels over the blocks of all windows, one scan, one cut, one gather, one checksum pass, one download,
+// ONE host wait.  No stream's state changes before the download has been checked.
+namespace {
+
+struct CsWin {
+  int32_t e;  // its entry
+  s3s_cs::CutEntry c;
+};
+
+struct CsBatch {
+  s3s_ctx* ctx;
+  s3s_cstream_feed_entry* E;
+  int32_t n;
+  std::vector<CsWin> W;
+  std::vector<int32_t> host;  // entries the single feed answers without device work, in order
+
+  void single(s3s_cstream_feed_entry& e) {
+    e.status = s3s_cstream_feed_device(e.stream, e.d_src, e.src_len, e.part_ends, e.n_ends, e.d_dst, e.dst_capacity, e.out_lengths,
+                                       e.out_checksums, &e.result);
+  }
+  int first_error() {
+    for (int32_t i = 0; i < n; i++)
+      if (E[i].status != S3S_OK) {
+        char msg[sizeof ctx->err];
+        snprintf(msg, sizeof msg, "%s", ctx->err);
+        return fail(ctx, E[i].status, "entry %d of the batch failed%s%.400s", i, msg[0] ? ": " : "", msg);
+      }
+    return S3S_OK;
+  }
+};
+
+inline int64_t unit_items(int codec, const s3s_cs::Unit& u) { return codec == S3S_CODEC_SNAPPY ? u.first + snappy_chunk_items(u.len) : 1; }
+inline int64_t unit_slots(int codec, const s3s_cs::Unit& u) { return codec == S3S_CODEC_SNAPPY ? snappy_chunk_slots(u.len) : u.len > 0; }
+
+// worst-case checksum segments of a window's pieces, as the single feed sizes them; seg_start (or null): n_ends + 2 entries
+int64_t window_segs(int codec, int64_t bs, int64_t src_len, const int64_t* ends, int32_t n_ends, int32_t* seg_start) {
+  int64_t segs = 0;
+  for (int32_t j = 0; j <= n_ends; j++) {
+    const int64_t a = j == 0 ? 0 : ends[j - 1], b = j < n_ends ? ends[j] : src_len;
+    if (seg_start) seg_start[j] = (int32_t)segs;
+    segs += worst_segs(max_partition_size(codec, bs, b - a) + kLz4FrameHeader + kSnappyStreamHeader);
+    if (segs > s3s_cs::kBatchMax) return -1;
+  }
+  if (seg_start) seg_start[n_ends + 1] = (int32_t)segs;
+  return segs;
+}
+
+// call-level refusals: nothing has been touched.  *batched: these streams go through the batched path
+int cs_batch_check(CsBatch& b, bool* batched, bool* any_enc) {
+  s3s_ctx* ctx = b.ctx;
+  *batched = b.n > 1 && !enc_on(ctx);
+  *any_enc = false;
+  std::vector<const s3s_cstream*> seen;
+  seen.reserve((size_t)b.n);
+  for (int32_t i = 0; i < b.n; i++) {
+    const s3s_cstream* s = b.E[i].stream;
+    if (!s) return fail(ctx, S3S_E_INVALID, "entry %d: null stream", i);
+    if (s->ctx != ctx) return fail(ctx, S3S_E_INVALID, "entry %d: the stream was opened on another context", i);
+    const s3s_cstream* s0 = b.E[0].stream;
+    if (s->codec != s0->codec || s->algo != s0->algo)
+      return fail(ctx, S3S_E_INVALID, "entry %d: the streams of a batch must share codec and checksum algorithm", i);
+    if (s->enc) *any_enc = true;
+    if (s->enc || s->codec == S3S_CODEC_NONE || s->bs != s0->bs || s->lz4_variant != s0->lz4_variant || s->snappy_variant != s0->snappy_variant)
+      *batched = false;
+    seen.push_back(s);
+  }
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(ctx, S3S_E_INVALID, "the same stream twice in one batch");
+  return S3S_OK;
+}
+
+// one by one, in order.  Encrypted streams: the call's IVs are sliced in entry order, n_ends + 1 an entry
+int cs_one_by_one(CsBatch& b, bool any_enc) {
+  s3s_ctx* ctx = b.ctx;
+  if (any_enc && enc_on(ctx)) {  // (with the layer off every encrypted stream is stale: the single feed's refusal)
+    int64_t want = 0;
+    for (int32_t i = 0; i < b.n; i++) want += (int64_t)(b.E[i].n_ends > 0 ? b.E[i].n_ends : 0) + 1;
+    if (ctx->iv_cur_n != want)
+      return fail(ctx, S3S_E_INVALID, "the entries of the batch have %lld pieces (n_ends + 1 each), s3s_set_stream_ivs gave %lld IVs",
+                  (long long)want, (long long)ctx->iv_cur_n);
+    const uint8_t* ivs = ctx->iv_cur;
+    for (int32_t i = 0; i < b.n; i++) {
+      const int64_t mine = (int64_t)(b.E[i].n_ends > 0 ? b.E[i].n_ends : 0) + 1;
+      ctx->iv_cur = ivs;
+      ctx->iv_cur_n = mine;
+      ivs += 16 * (size_t)mine;
+      b.single(b.E[i]);
+    }
+    return S3S_OK;
+  }
+  for (int32_t i = 0; i < b.n; i++) b.single(b.E[i]);
+  return S3S_OK;
+}
+
+// Which entries are windows of the batch: those whose single feed would launch something.  An entry the single feed refuses
+// by its arguments, and one whose window launches nothing, keep that feed's answer (b.host).  false: the call does not fit one
+// plan (an index would leave int32): it goes one by one
+bool cs_batch_windows(CsBatch& b, s3s_cs::Totals* tot) {
+  const s3s_cstream* s0 = b.E[0].stream;
+  const int codec = s0->codec;
+  const int64_t bs = s0->bs;
+  const bool do_sum = s0->algo != S3S_CHECKSUM_NONE;
+  for (int32_t i = 0; i < b.n; i++) {
+    const s3s_cstream_feed_entry& e = b.E[i];
+    const s3s_cstream* s = e.stream;
+    const bool null_with_length = (e.src_len > 0 && !e.d_src) || (e.dst_capacity > 0 && !e.d_dst) ||
+                                  (e.n_ends > 0 && (!e.part_ends || !e.out_lengths || (do_sum && !e.out_checksums)));
+    const bool refused = s3s_cs::window_refused(e.src_len, e.part_ends, e.n_ends, e.dst_capacity, null_with_length);
+    int64_t n_items = 0, n_slots = 0;
+    if (!refused)
+      s3s_cs::plan_units(codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, [&](const s3s_cs::Unit& u) {
+        n_items += unit_items(codec, u);
+        n_slots += unit_slots(codec, u);
+      });
+    if (refused || n_items == 0 || n_items > s3s_cs::kBatchMax) {  // (too many blocks: the single feed's S3S_E_UNSUPPORTED)
+      b.host.push_back(i);
+      continue;
+    }
+    const int64_t segs = do_sum ? window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, nullptr) : 0;
+    if (segs < 0) {  // (window too large for one feed: the single feed's answer)
+      b.host.push_back(i);
+      continue;
+    }
+    if (!s3s_cs::fits_call(*tot, n_items, n_slots, e.n_ends, segs)) return false;
+    CsWin w;
+    w.e = i;
+    w.c = s3s_cs::reserve(tot, n_items, n_slots, e.n_ends, segs, e.dst_capacity, s->st.open_img);
+    b.W.push_back(w);
+  }
+  return true;
+}
+
+int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
+  s3s_ctx* ctx = b.ctx;
+  const s3s_cstream* s0 = b.E[0].stream;
+  const int codec = s0->codec, algo = s0->algo;
+  const int64_t bs = s0->bs;
+  const bool do_sum = algo != S3S_CHECKSUM_NONE;
+  const int32_t m = tot.m, N = (int32_t)tot.items;
+  const size_t PP = (size_t)tot.pp(), P = (size_t)tot.pieces;
+  s3s_cs::Arena A;
+  A.lay_out(tot, sizeof(Item), sizeof(TaskTail));
+  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
+  int rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if ((rc = ensure_stage(ctx, A.total))) return rc;
+  if ((rc = ensure(ctx, B_PLAN, A.total))) return rc;
+  if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(tot.slots > 0 ? tot.slots : 1)))) return rc;  // a slot for every block of EVERY window
+  if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * ((size_t)N + 1)))) return rc;
+  if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * ((size_t)N + (size_t)m + 1)))) return rc;
+  if ((rc = ensure(ctx, B_ITEM_CHECK, sizeof(uint32_t) * ((size_t)N + 1)))) return rc;
+  if ((rc = ensure(ctx, B_WORK, 64))) return rc;
+  if ((rc = ensure(ctx, B_OFFSETS, 8 * PP))) return rc;
+  if (do_sum && (rc = ensure(ctx, B_PARTIAL, 16 * (size_t)(tot.segs > 0 ? tot.segs : 1)))) return rc;
+  uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
+  uint8_t* da = dev<uint8_t>(ctx, B_PLAN);
+  Item* h_items = reinterpret_cast<Item*>(hs + A.items);
+  s3s_cs::Mark* h_marks = reinterpret_cast<s3s_cs::Mark*>(hs + A.marks);
+  int32_t* h_pf = reinterpret_cast<int32_t*>(hs + A.pf);
+  int32_t* h_seg = reinterpret_cast<int32_t*>(hs + A.seg);
+  int64_t* h_seed = reinterpret_cast<int64_t*>(hs + A.seed);
+  int32_t* h_pw = reinterpret_cast<int32_t*>(hs + A.pw);
+  TaskTail* h_tails = reinterpret_cast<TaskTail*>(hs + A.tails);
+  s3s_cs::CutEntry* h_cuts = reinterpret_cast<s3s_cs::CutEntry*>(hs + A.cuts);
+
+  const uint8_t* base = b.E[b.W[0].e].d_src;  // the one source pointer of the codec launch: every item is an offset from it
+  const int level = codec == S3S_CODEC_LZ4 ? lz4_level(bs) : 0;
+  memset(hs + A.seg, 0, A.seed - A.seg);
+  for (int32_t wi = 0; wi < m; wi++) {
+    CsWin& w = b.W[(size_t)wi];
+    const s3s_cstream_feed_entry& e = b.E[w.e];
+    const s3s_cstream* s = e.stream;
+    const int64_t delta = s3s_cs::item_src_off((int64_t)reinterpret_cast<intptr_t>(e.d_src), (int64_t)reinterpret_cast<intptr_t>(base), 0);
+    const bool ok = s3s_cs::plan_entry(
+        &w.c, codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, h_marks, h_pf,
+        [&](const s3s_cs::Unit& u) { return unit_items(codec, u); },
+        [&](const s3s_cs::Unit& u, int32_t at, int32_t& slot) {
+          int32_t it = at;
+          if (codec == S3S_CODEC_SNAPPY) {
+            if (u.first) h_items[it++] = Item{0, 0, kItemSnappyHeader, -1, u.piece};
+            snappy_plan_chunk(h_items, it, slot, delta + u.src_off, u.len, u.piece);
+          } else if (codec == S3S_CODEC_LZF) {
+            h_items[it] = Item{delta + u.src_off, u.len, kItemLzfChunk, slot++, u.piece};
+          } else if (u.len > 0) {
+            h_items[it] = Item{delta + u.src_off, u.len, lz4_chunk_kind(u.len) | (level << 8), slot++, u.piece};
+          } else {
+            h_items[it] = Item{0, 0, kItemLz4End | (level << 8), -1, u.piece};
+          }
+        });
+    if (!ok) return fail(ctx, S3S_E_HIP, "the plan of entry %d does not match its count", w.e);
+    if (do_sum) window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, h_seg + w.c.first_pp);
+    s3s_cs::seed_pieces(w.c, wi, s->carry, fresh(algo), h_seed, h_pw);
+    h_cuts[wi] = w.c;
+    TaskTail& t = h_tails[wi];
+    t.first_item = w.c.first_item;
+    t.n_items = w.c.n_items;
+    t.first_pp = w.c.first_pp;
+    t.n_parts = w.c.n_pieces;
+    t.first_part = w.c.first_piece;
+    t.first_seg = w.c.first_seg;
+    t.n_segs = w.c.n_segs;
+    t.pad = 0;
+    t.data = e.d_dst;
+    t.data_len = e.dst_capacity;
+    t.dst = e.d_dst;
+    t.dst_capacity = e.dst_capacity;
+  }
+
+  const TaskTail* d_tails = reinterpret_cast<const TaskTail*>(da + A.tails);
+  const Item* d_items = reinterpret_cast<const Item*>(da + A.items);
+  const int32_t* d_pf = reinterpret_cast<const int32_t*>(da + A.pf);
+  int32_t* d_status = reinterpret_cast<int32_t*>(da + A.status);
+  int64_t* d_result = reinterpret_cast<int64_t*>(da + A.res);
+  int64_t* d_piece = reinterpret_cast<int64_t*>(da + A.piece);
+  int64_t* d_len = reinterpret_cast<int64_t*>(da + A.len);
+  int64_t* d_sums = reinterpret_cast<int64_t*>(da + A.sums);
+  HIP_TRY(ctx, hipMemcpyAsync(da, hs, A.up, hipMemcpyHostToDevice, ctx->stream));  // the call's one upload
+  HIP_TRY(ctx, hipMemsetAsync(da + A.up, 0, A.total - A.up, ctx->stream));
+  if (codec == S3S_CODEC_LZ4) {
+    ctx->lz4_variant_used = s0->lz4_variant;
+    launch_lz4_compress(base, d_items, N, dev<uint32_t>(ctx, B_ITEM_CHECK), dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride,
+                        dev<uint32_t>(ctx, B_ITEM_SIZE), dev<uint32_t>(ctx, B_WORK), (s0->lz4_variant == 11 ? 8 : 10) * ctx->cu_count,
+                        s0->lz4_variant, ctx->stream, nullptr, bs >= kLz4U32From);
+  } else if (codec == S3S_CODEC_LZF) {
+    launch_lzf_compress(base, d_items, N, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);
+  } else {
+    launch_snappy_compress(base, d_items, N, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), s0->snappy_variant,
+                           ctx->stream);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  // (the scan's own index - the unclamped piece offsets - goes to a buffer nobody reads: the cut kernel writes the clamped ones)
+  launch_scan_items_batch(d_tails, m, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF), d_pf, dev<int64_t>(ctx, B_OFFSETS),
+                          ctx->stream);
+  launch_cstream_cut_batch(da + A.cuts, m, da + A.marks, dev<int64_t>(ctx, B_ITEM_OFF), d_pf, d_result, d_piece, d_len, ctx->stream);
+  launch_gather_items_cut_batch(d_tails, m, N, base, d_items, d_result, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
+                                dev<int64_t>(ctx, B_ITEM_OFF), d_status, ctx->stream);
+  if (do_sum) {  // over the pieces as the cuts left them; a stream's carried state seeds its window's first piece
+    launch_checksum_batch(algo, d_tails, m, (int32_t)tot.segs, (int32_t)P, d_piece, reinterpret_cast<const int32_t*>(da + A.seg),
+                          ctx->buf[B_TABLES].p, dev<uint32_t>(ctx, B_PARTIAL), d_sums, ctx->stream);
+    launch_checksum_seed_batch(algo, d_piece, reinterpret_cast<const int32_t*>(da + A.pw), (int32_t)P, ctx->buf[B_TABLES].p,
+                               reinterpret_cast<const int64_t*>(da + A.seed), d_sums, ctx->stream);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(hs + A.up, da + A.up, A.total - A.up, hipMemcpyDeviceToHost, ctx->stream));  // the call's one download
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                                          // ... and its one wait
+
+  // every window's words are checked before any stream moves
+  const int32_t* h_status = reinterpret_cast<const int32_t*>(hs + A.status);
+  const int64_t* h_res = reinterpret_cast<const int64_t*>(hs + A.res);
+  std::vector<s3s_cs::Cut> cuts((size_t)m);
+  for (int32_t wi = 0; wi < m; wi++) {
+    const CsWin& w = b.W[(size_t)wi];
+    const s3s_cstream_feed_entry& e = b.E[w.e];
+    if (!s3s_cs::cut_from_words(h_res + (size_t)s3s_cs::kCutWords * (size_t)wi, h_status[wi], w.c.n_items, e.src_len, e.dst_capacity, e.n_ends,
+                                &cuts[(size_t)wi]))
+      return fail(ctx, S3S_E_HIP, "the capacity cut of entry %d returned an impossible result", w.e);
+  }
+  for (int32_t wi = 0; wi < m; wi++) {
+    const CsWin& w = b.W[(size_t)wi];
+    s3s_cstream_feed_entry& e = b.E[w.e];
+    s3s_cstream* s = e.stream;
+    const s3s_cs::Cut& c = cuts[(size_t)wi];
+    memset(&e.result, 0, sizeof e.result);
+    if (c.need_dst > 0) {  // the window's first unit does not fit its dst: nothing is taken, the stream stays usable
+      e.result.need_dst = c.need_dst;
+      e.status = fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld image bytes of the next unit", (long long)e.dst_capacity, (long long)c.need_dst);
+      continue;
+    }
+    s3s_cs::commit(&s->st, &s->carry, c, e.part_ends, reinterpret_cast<const int64_t*>(hs + A.piece) + w.c.first_pp,
+                   reinterpret_cast<const int64_t*>(hs + A.len) + w.c.first_len,
+                   do_sum ? reinterpret_cast<const int64_t*>(hs + A.sums) + w.c.first_piece : nullptr, e.out_lengths, e.out_checksums);
+    e.result.consumed = c.consumed;
+    e.result.out_len = c.out_len;
+    e.result.parts_closed = c.parts_closed;
+    e.status = S3S_OK;
+  }
+  return S3S_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int s3s_cstream_feed_batch_device(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32_t n) {
+  if (!ctx) return S3S_E_INVALID;
+  ctx->err[0] = 0;
+  ctx->cstream_batch_entries = 0;  // S3S_OPT_CSTREAM_BATCH_ENTRIES: set where the batched path has answered
+  std::optional<IvScope> iv_scope;  // under IO encryption the call is a compress call: it consumes the IVs of s3s_set_stream_ivs either way
+  if (enc_on(ctx)) iv_scope.emplace(ctx);
+  if (n < 0 || (n > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  BatchVerdict<s3s_cstream_feed_entry> verdict(E, n);
+  if (n == 0) return verdict.finish(S3S_OK);
+  CsBatch b = {ctx, E, n, {}, {}};
+  bool batched, any_enc;
+  int rc;
+  if ((rc = cs_batch_check(b, &batched, &any_enc))) return rc;
+  s3s_cs::Totals tot;
+  if (batched && !cs_batch_windows(b, &tot)) {
+    batched = false;
+    b.W.clear();
+    b.host.clear();
+  }
+  if (!batched) {  // nothing to batch: one by one, in order
+    if ((rc = cs_one_by_one(b, any_enc))) return rc;
+    return verdict.finish(b.first_error());
+  }
+  if (tot.m > 0 && (rc = cs_batch_run(b, tot))) return rc;
+  for (int32_t i : b.host) b.single(E[i]);  // (no device work: an argument the single feed refuses, a window that launches nothing)
+  ctx->cstream_batch_entries = tot.m;
+  return verdict.finish(b.first_error());
+}
+
+int s3s_cstream_feed_batch(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32_t n) {
+  if (!ctx) return S3S_E_INVALID;
+  ctx->err[0] = 0;
+  ctx->cstream_batch_entries = 0;
+  if (n < 0 || (n > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  BatchVerdict<s3s_cstream_feed_entry> verdict(E, n);
+  if (n == 0) return verdict.finish(S3S_OK);
+  // the windows and the destinations of ALL entries are staged in the context's workspace: the sum of src_len + dst_capacity
+  // is the caller's memory bound.  An entry the single feed refuses by its buffers is staged as empty and keeps them
+  auto al = [](int64_t x) { return (x + 255) & ~int64_t(255); };
+  auto staged = [](const s3s_cstream_feed_entry& e) {
+    return e.src_len >= 0 && e.dst_capacity >= 0 && (e.src_len == 0 || e.d_src) && (e.dst_capacity == 0 || e.d_dst);
+  };
+  std::vector<s3s_cstream_feed_entry> D(E, E + n);
+  std::vector<int64_t> so((size_t)n), dso((size_t)n);
+  int64_t src_total = 0, dst_total = 0;
+  for (int32_t i = 0; i < n; i++) {
+    so[(size_t)i] = src_total;
+    dso[(size_t)i] = dst_total;
+    if (staged(E[i])) {
+      src_total += al(E[i].src_len + 64);
+      dst_total += al(E[i].dst_capacity + 64);
+    }
+  }
+  std::optional<IvScope> iv_scope;  // (the device form's scope nests in this one)
+  if (enc_on(ctx)) iv_scope.emplace(ctx);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = ensure(ctx, B_SRC, (size_t)src_total + 64))) return rc;
+  if ((rc = ensure(ctx, B_DST, (size_t)dst_total + 64))) return rc;
+  for (int32_t i = 0; i < n; i++) {
+    const s3s_cstream_feed_entry& e = E[i];
+    if (!staged(e)) {  // the device form's single feed answers S3S_E_INVALID from the same arguments (a null pointer stays null)
+      D[(size_t)i].d_src = e.d_src ? dev<uint8_t>(ctx, B_SRC) : nullptr;
+      D[(size_t)i].d_dst = e.d_dst ? dev<uint8_t>(ctx, B_DST) : nullptr;
+      continue;
+    }
+    D[(size_t)i].d_src = e.src_len > 0 ? dev<uint8_t>(ctx, B_SRC) + so[(size_t)i] : nullptr;
+    D[(size_t)i].d_dst = e.dst_capacity > 0 ? dev<uint8_t>(ctx, B_DST) + dso[(size_t)i] : nullptr;
+    if (e.src_len > 0) HIP_TRY(ctx, hipMemcpyAsync(dev<uint8_t>(ctx, B_SRC) + so[(size_t)i], e.d_src, (size_t)e.src_len, hipMemcpyHostToDevice, ctx->stream));
+  }
+  rc = s3s_cstream_feed_batch_device(ctx, D.data(), n);
+  for (int32_t i = 0; i < n; i++) {
+    E[i].result = D[(size_t)i].result;
+    E[i].status = D[(size_t)i].status;
+  }
+  for (int32_t i = 0; i < n; i++)
+    if (E[i].status == S3S_OK && E[i].result.out_len > 0)
+      HIP_TRY(ctx, hipMemcpyAsync(E[i].d_dst, D[(size_t)i].d_dst, (size_t)E[i].result.out_len, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return verdict.finish(rc);
 }
 
 }  // extern "C"

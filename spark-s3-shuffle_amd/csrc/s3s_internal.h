@@ -381,6 +381,17 @@ void launch_gather_items_cut(const uint8_t* d_src, const Item* d_items, int32_t 
                              const uint8_t* d_slots, int64_t slot_stride, const uint32_t* d_item_size,
                              const int64_t* d_item_off, uint8_t* d_dst, int64_t dst_capacity,
                              int32_t* d_status, hipStream_t st);
+// ---- batched feed of the streaming map side (compress_stream.hip: s3s_cstream_feed_batch*; kernels:
+//      compress_stream_batch_kernels.hip; the layout of the call's packed arrays: compress_stream_batch_core.h) -----------------
+//   launch_cstream_cut for the windows of all entries, one wavefront each.  d_cuts: one s3s_cs::CutEntry per entry; d_marks,
+//   d_item_off, d_part_first and the three outputs are the call's packed arrays (d_result: s3s_cs::kCutWords words an entry)
+void launch_cstream_cut_batch(const void* d_cuts, int32_t n_entries, const void* d_marks, const int64_t* d_item_off,
+                              const int32_t* d_part_first, int64_t* d_result, int64_t* d_piece_off, int64_t* d_lengths, hipStream_t st);
+//   launch_gather_items_cut over the items of all entries: entry e's items [0, d_result[kCutWords e]) go to d_tails[e].dst and
+//   never at or beyond d_tails[e].dst_capacity; d_status: one word an entry
+void launch_gather_items_cut_batch(const TaskTail* d_tails, int32_t n_entries, int32_t n_items_total, const uint8_t* d_src,
+                                   const Item* d_items, const int64_t* d_result, const uint8_t* d_slots, int64_t slot_stride,
+                                   const uint32_t* d_item_size, const int64_t* d_item_off, int32_t* d_status, hipStream_t st);
 
 // ---- device helpers shared by several kernels --------------------------------------------
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) {

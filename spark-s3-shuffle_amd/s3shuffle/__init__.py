@@ -18,6 +18,7 @@ from .codec import (  # noqa: F401
     CODEC_ZSTD,
     Codec,
     CodecError,
+    CompressFeedEntry,
     CompressStream,
     CompressStreamResult,
     DecodeStream,

@@ -28,6 +28,7 @@ OPT_ZSTD_DECODE_VARIANT = 13  # ABI 11, additive: 1 (default) = block-independen
 OPT_ZSTD_DECODE_BLOCKS = 14  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the block path
 OPT_ZSTD_DECODE_STAGED = 15  # ABI 11, additive: 0 (default) / 1 = Zstandard frames with history across blocks decode in stages (entropy per block, copies per frame)
 OPT_ZSTD_DECODE_STAGED_BLOCKS = 16  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the staged path
+OPT_CSTREAM_BATCH_ENTRIES = 18  # ABI 11, additive, read-only: entries of the last compress_stream_feed_batch* call that the batched path answered
 OPT_DSTREAM_BATCH_ENTRIES = 17  # ABI 11, additive, read-only: entries of the last feed_streams* call that the batched path answered (0: it went one by one)
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
@@ -99,6 +100,14 @@ class CompressStreamResult(ctypes.Structure):
     """s3s_cstream_result (include/s3shuffle_codec.h): what one feed of a CompressStream did."""
     _fields_ = [("consumed", ctypes.c_int64), ("out_len", ctypes.c_int64), ("need_src", ctypes.c_int64),
                 ("need_dst", ctypes.c_int64), ("parts_closed", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class CompressFeedEntry(ctypes.Structure):
+    """s3s_cstream_feed_entry (include/s3shuffle_codec.h): one stream's window in a batched feed of the map side."""
+    _fields_ = [("stream", ctypes.c_void_p), ("d_src", ctypes.c_void_p), ("src_len", ctypes.c_int64),
+                ("part_ends", ctypes.POINTER(ctypes.c_int64)), ("n_ends", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("d_dst", ctypes.c_void_p), ("dst_capacity", ctypes.c_int64), ("out_lengths", ctypes.POINTER(ctypes.c_int64)),
+                ("out_checksums", ctypes.POINTER(ctypes.c_int64)), ("result", CompressStreamResult)]
 
 
 def load_library() -> ctypes.CDLL:
@@ -206,6 +215,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "s3s_dstream_feed_batch_device"):  # the batched feed (additive, detected by the symbols)
         lib.s3s_dstream_feed_batch_device.argtypes = [vp, ctypes.POINTER(FeedEntry), ctypes.c_int32]
         lib.s3s_dstream_feed_batch.argtypes = lib.s3s_dstream_feed_batch_device.argtypes
+    if hasattr(lib, "s3s_cstream_feed_batch_device"):  # the batched feed of the map side (additive, detected by the symbols)
+        lib.s3s_cstream_feed_batch_device.argtypes = [vp, ctypes.POINTER(CompressFeedEntry), ctypes.c_int32]
+        lib.s3s_cstream_feed_batch.argtypes = lib.s3s_cstream_feed_batch_device.argtypes
     _LIB = lib
     return lib
 
@@ -453,6 +465,68 @@ class Codec:
         s3s_cstream_open_encrypted (capacities, lengths and `written` count the stored bytes, IVs included; set_stream_ivs
         with `len(part_ends) + 1` IVs goes in front of every feed)."""
         return CompressStream(self, codec, checksum, encrypted=encrypted)
+
+    @property
+    def compress_batch_entries(self) -> int:
+        """Entries of the last compress_stream_feed_batch* call that the batched path answered; 0 when it went one by one or was refused."""
+        return self.get_option(OPT_CSTREAM_BATCH_ENTRIES)
+
+    def compress_stream_feed_batch(self, entries, _host: bool = False):
+        """The batched feed of the map side (s3s_cstream_feed_batch_device): `entries` = [(CompressStream, d_src, src_len,
+        part_ends, d_dst, dst_capacity), ...], one window of each of several streams of this context -> per entry the
+        CompressStreamResult that `stream.feed_device` alone would have given, with `.code`, `.lengths` and `.checksums` (None
+        when the stream has no checksums).  Nothing is raised for an entry's own verdict; `last_compress_batch_code` is the
+        call's return code (the first entry's that is not S3S_OK, or S3S_E_INVALID with every entry S3S_STATUS_NOT_RUN)."""
+        if not hasattr(self._lib, "s3s_cstream_feed_batch_device"):
+            raise CodecError(E_UNSUPPORTED, "this build of the library has no s3s_cstream_feed_batch_device")
+        arr = (CompressFeedEntry * max(len(entries), 1))()
+        keep = []
+        for i, (stream, d_src, src_len, part_ends, d_dst, cap) in enumerate(entries):
+            ends = _i64(part_ends)
+            n = len(ends)
+            lengths = np.zeros(max(n, 1), dtype=np.int64)
+            with_sums = getattr(stream, "_checksum", CHECKSUM_ADLER32) != CHECKSUM_NONE
+            sums = np.zeros(max(n, 1), dtype=np.int64) if with_sums else None
+            keep.append((ends, lengths, sums))
+            arr[i].stream = getattr(stream, "_s", stream)  # a CompressStream, or a raw handle (None: a null stream)
+            arr[i].d_src = d_src if src_len else None
+            arr[i].src_len = int(src_len)
+            arr[i].part_ends = _p64(ends) if n else None
+            arr[i].n_ends = n
+            arr[i].d_dst = d_dst if cap else None
+            arr[i].dst_capacity = int(cap)
+            arr[i].out_lengths = _p64(lengths) if n else None
+            arr[i].out_checksums = _p64(sums) if (n and sums is not None) else None
+        fn = self._lib.s3s_cstream_feed_batch if _host else self._lib.s3s_cstream_feed_batch_device
+        self.last_compress_batch_code = int(fn(self._h, arr, len(entries)))
+        out = []
+        for i, e in enumerate(entries):
+            r = CompressStreamResult.from_buffer_copy(arr[i].result)
+            r.code = int(arr[i].status)
+            closed = r.parts_closed if r.code == 0 else 0
+            r.lengths = keep[i][1][:closed]
+            r.checksums = keep[i][2][:closed] if keep[i][2] is not None else None
+            if hasattr(e[0], "last_result"):
+                e[0].last_result = r
+            out.append(r)
+        return out
+
+    def compress_stream_feed_batch_host(self, entries):
+        """The host-buffer form (s3s_cstream_feed_batch): `entries` = [(CompressStream, src, part_ends, dst), ...] or
+        [(CompressStream, src, part_ends, dst, dst_capacity), ...] with uint8 arrays; the image bytes land in
+        dst[:result.out_len].  The library stages the windows and destinations of ALL entries on the device: the sum of their
+        sizes is the memory bound."""
+        rows, keep = [], []
+        for e in entries:
+            stream, src, ends, dst = e[0], np.ascontiguousarray(e[1], dtype=np.uint8), e[2], e[3]
+            if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable):
+                raise ValueError("dst must be a writable C-contiguous uint8 array (the library writes into it)")
+            cap = dst.size if len(e) < 5 or e[4] is None else int(e[4])
+            if not 0 <= cap <= dst.size:
+                raise ValueError(f"dst_capacity {cap} is outside dst's {dst.size} bytes")
+            keep.append(src)
+            rows.append((stream, src.ctypes.data, src.size, ends, dst.ctypes.data, cap))
+        return self.compress_stream_feed_batch(rows, _host=True)
 
     # ---- reduce side ---------------------------------------------------------------------------
     def decode_stream(self, codec: int, checksum: int, part_offsets, ref_checksums=None, encrypted: bool = False,

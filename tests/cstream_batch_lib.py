@@ -1,0 +1,268 @@
+"""Helpers of tests/test_compress_stream_batch_cpu.py: the stand-alone model program of the batched feed's host arithmetic
+(tests/model/cstream_batch_model.cpp over csrc/compress_stream_batch_core.h), the Python stand-in that plays the kernels for
+it over a pipe, and the rounds that drive both against tests/cstream_units.Model."""
+import os
+import subprocess
+import zlib
+
+import numpy as np
+
+import cstream_units as cu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "spark-s3-shuffle_amd", "csrc")
+CORE = os.path.join(CSRC, "compress_stream_batch_core.h")
+MODEL = os.path.join(ROOT, "tests", "model", "cstream_batch_model.cpp")
+ADLER, CRC = 1, 2
+SENTINEL = -7
+
+
+class Dead(AssertionError):
+    """the program stopped (a sanitizer report, an exit code), or the plan it printed cannot be played"""
+
+
+def build(out_dir, include_dir=CSRC):
+    exe = os.path.join(str(out_dir), "cstream_batch_model")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-I", include_dir, MODEL, "-o", exe], check=True)
+    return exe
+
+
+def checksum(algo, data, seed):
+    if not algo:
+        return 0
+    return (zlib.adler32(data, seed) if algo == ADLER else zlib.crc32(data, seed)) & 0xFFFFFFFF
+
+
+def fresh(algo):
+    return 1 if algo == ADLER else 0
+
+
+class StreamCase:
+    """one stream of a run: its map output, the one-shot image, and the model of the contract"""
+
+    def __init__(self, oracle, codec, bs, data, offs):
+        self.codec, self.bs, self.data, self.offs = codec, bs, data, [int(x) for x in offs]
+        img, index, _ = oracle.compress_map_output(codec, 0, data, offs, block_size=bs if codec in (cu.LZ4, cu.SNAPPY) else 32768)
+        self.img, self.index = np.asarray(img).tobytes(), [int(x) for x in index]
+        self.sizes = cu.unit_sizes_from_image(codec, self.img, self.index)
+        self.model = cu.Model(codec, bs, self.sizes)
+
+    @property
+    def done(self):
+        return self.model.pos >= self.offs[-1] and self.model.n_closed >= len(self.offs) - 1
+
+    def item_size(self, stream_off, length):
+        """image bytes of the block item whose source is [stream_off, stream_off + length) (Snappy: without the stream header)"""
+        p = int(np.searchsorted(self.offs, stream_off, side="right")) - 1  # (of equal offsets the last: the partition that has bytes)
+        if not 0 <= p < len(self.offs) - 1:
+            raise Dead("no block of the map output starts at %d" % stream_off)
+        rel = stream_off - self.offs[p]
+        if rel % self.bs or length != min(self.bs, self.offs[p + 1] - stream_off) or not 0 <= rel // self.bs < len(self.sizes[p]):
+            raise Dead("no block of the map output is [%d, +%d)" % (stream_off, length))
+        size = self.sizes[p][rel // self.bs]
+        return size - 16 if self.codec == cu.SNAPPY and rel == 0 else size
+
+
+class Program:
+    def __init__(self, exe, tmp_path, codec, bs, algo, n_streams):
+        self.err = open(os.path.join(str(tmp_path), "stderr.txt"), "w+")
+        self.p = subprocess.Popen([exe], stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=self.err, text=True, bufsize=1)
+        self.algo = algo
+        self.p.stdin.write("%d %d %d %d %d\n" % (codec, bs, fresh(algo), 1 if algo else 0, n_streams))
+
+    def _line(self):
+        line = self.p.stdout.readline()
+        if not line:
+            self.p.wait(timeout=60)
+            self.err.seek(0)
+            raise Dead("the model program stopped (exit %s): %s" % (self.p.returncode, self.err.read()[-3000:]))
+        return line.split()
+
+    def _ints(self, tag):
+        t = self._line()
+        if t[0] != tag:
+            raise Dead("expected %s, got %s" % (tag, t[:4]))
+        return [int(x) for x in t[1:]]
+
+    def round(self, entries, streams):
+        """entries: [(stream index, addr, src_len, cap, ends or None (n_ends = -1))] -> per entry dict of the answer.
+        streams: the StreamCases, BEFORE their models are advanced (the stand-in reads pos / written from them)."""
+        text = "R %d\n" % len(entries)
+        for s, addr, src_len, cap, ends in entries:
+            text += "%d %d %d %d %d %s\n" % (s, addr, src_len, cap, -1 if ends is None else len(ends), " ".join(map(str, ends or [])))
+        try:
+            self.p.stdin.write(text)
+            self.p.stdin.flush()
+        except BrokenPipeError:
+            self._line()
+        t = self._line()
+        windows = 0
+        if t[0] == "P":
+            m, N, PP, P, L = (int(x) for x in t[1:])
+            windows = m
+            wins = [self._ints("W") for _ in range(m)]
+            items, marks, pf, seeds, pw = self._ints("I"), self._ints("M"), self._ints("F"), self._ints("S"), self._ints("E")
+            if not (len(items) == 4 * N and len(marks) == 3 * N and len(pf) == PP and len(seeds) == P and len(pw) == P):
+                raise Dead("the plan's arrays do not have the sizes it states")
+            down = self._kernels(entries, streams, wins, items, marks, pf, seeds, pw, N, PP, P, L)
+            try:
+                self.p.stdin.write(" ".join(str(int(x)) for x in down) + "\n")
+                self.p.stdin.flush()
+            except BrokenPipeError:
+                self._line()
+            t = self._line()
+            if t[0] == "X":
+                raise Dead("the program found the stand-in's words impossible")
+        out = []
+        for i in range(len(entries)):
+            if i:
+                t = self._line()
+            if t[0] != "A":
+                raise Dead("expected A, got %s" % t[:4])
+            v = [int(x) for x in t[1:]]
+            n = v[6]
+            d = dict(zip(("code", "consumed", "out_len", "need_src", "need_dst", "parts_closed"), v[:6]))
+            d["lengths"] = v[7:7 + n]
+            rest = v[7 + n:]
+            d["sums"] = rest[:n] if self.algo else []
+            d["pos"], d["written"], d["open_bytes"], d["open_img"], d["carry"] = rest[-5:]
+            out.append(d)
+        return out, windows
+
+    def _kernels(self, entries, streams, wins, items, marks, pf, seeds, pw, N, PP, P, L):
+        """the device side of the call, from the plan as the program laid it out: item sizes (the codec kernels), the scan, the
+        cut, the clamped piece offsets, the lengths, the seeded checksums - every array indexed as the kernels index it"""
+        m = len(wins)
+        status, res = [0] * m, [SENTINEL] * (8 * m)
+        piece, lens, sums = [SENTINEL] * PP, [SENTINEL] * L, [SENTINEL] * P
+        base = entries[wins[0][0]][1]
+        spans = [(e[1], e[1] + e[2], e[0]) for e in entries if e[2] > 0 and e[4] is not None]
+        for wi, (e, first_item, n_items, first_pp, n_pieces, first_piece, first_len, first_last, ends0, cap, open_img) in enumerate(wins):
+            if not (0 <= first_item and first_item + n_items <= N and 0 <= first_pp and first_pp + n_pieces + 1 <= PP and
+                    0 <= first_piece and first_piece + n_pieces <= P and 0 <= first_len and first_len + n_pieces - 1 <= L):
+                raise Dead("window %d lies outside the call's arrays" % wi)
+            size = []
+            for i in range(first_item, first_item + n_items):
+                src_off, length, kind, _ = items[4 * i:4 * i + 4]
+                if kind == 2:
+                    size.append(16)
+                elif kind == 1:
+                    size.append(cu.LZ4_END)
+                else:
+                    a = base + src_off
+                    hit = [(lo, s) for lo, hi, s in spans if lo <= a and a + length <= hi]
+                    if len(hit) != 1:
+                        raise Dead("item %d reads [%d, +%d): no window of the call" % (i, a, length))
+                    lo, s = hit[0]
+                    size.append(streams[s].item_size(streams[s].model.pos + a - lo, length))
+            off = [0]
+            for x in size:
+                off.append(off[-1] + x)
+            mk = [marks[3 * i:3 * i + 3] for i in range(first_item, first_item + n_items)]
+            best = max((i for i in range(n_items) if mk[i][1] and off[i + 1] <= cap), default=-1)
+            k, out_len = best + 1, off[best + 1]
+            closed = mk[best][2] if best >= 0 else ends0
+            res[8 * wi:8 * wi + 5] = [k, mk[best][0] if best >= 0 else 0, out_len,
+                                      off[first_last + 1] if best < 0 and first_last >= 0 and ends0 == 0 else 0, closed]
+            for p in range(n_pieces + 1):
+                lo = min(off[pf[first_pp + p]], out_len)
+                piece[first_pp + p] = lo
+                if p < n_pieces - 1:
+                    b = min(off[pf[first_pp + p + 1]], out_len)
+                    lens[first_len + p] = b - lo + (open_img if p == 0 else 0) if p < closed else 0
+            sc = streams[entries[e][0]]
+            image = sc.img[sc.model.written:sc.model.written + out_len]
+            for j in range(n_pieces):
+                if pw[first_piece + j] != wi:
+                    raise Dead("piece %d of window %d belongs to window %d" % (j, wi, pw[first_piece + j]))
+                sums[first_piece + j] = checksum(self.algo, image[piece[first_pp + j]:piece[first_pp + j + 1]], seeds[first_piece + j])
+        return status + res + piece + lens + sums
+
+    def kill(self):
+        """after a failed round: the program is not left waiting for the next one"""
+        self.p.kill()
+        self.p.wait(timeout=60)
+        self.err.close()
+
+    def close(self):
+        self.p.stdin.close()
+        rc = self.p.wait(timeout=60)
+        self.err.seek(0)
+        text = self.err.read()
+        if rc != 0 or text:
+            raise Dead("exit %s: %s" % (rc, text[-3000:]))
+
+
+def map_output(rng, bs, shape):
+    """partition sizes with empty ones first, in the middle and last"""
+    sizes = [0] + [int(rng.choice([0, 1, bs - 1, bs, bs + 1, 2 * bs, int(rng.integers(1, 3 * bs))])) for _ in range(shape)] + [0]
+    sizes[len(sizes) // 2] = 0
+    total = sum(sizes)
+    data = np.resize(np.frombuffer(b"abcdefgh01234567abcdefgh", np.uint8), total).copy()
+    data[total // 2:] = rng.integers(0, 256, total - total // 2, dtype=np.uint8)
+    return data, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def run_rounds(oracle, exe, tmp_path, codec, bs, algo, seed, n_streams, max_rounds=300):
+    """random rounds of one window of each of n_streams streams until every stream has closed its map output; every answer
+    and every stream's state is compared with the model.  -> (rounds, windows batched, entries refused, entries answered on the host)"""
+    rng = np.random.default_rng(seed)
+    streams = [StreamCase(oracle, codec, bs, *map_output(rng, bs, int(rng.integers(2, 6)))) for _ in range(n_streams)]
+    prog = Program(exe, tmp_path, codec, bs, algo, n_streams)
+    big = max(max((x for p in s.sizes for x in p), default=1) for s in streams)
+    rounds = batched = refused = hosted = 0
+    try:
+        return _rounds(prog, streams, rng, codec, bs, algo, seed, big, max_rounds)
+    except BaseException:
+        prog.kill()
+        raise
+
+
+def _rounds(prog, streams, rng, codec, bs, algo, seed, big, max_rounds):
+    n_streams = len(streams)
+    rounds = batched = refused = hosted = 0
+    while not all(s.done for s in streams) and rounds < max_rounds:
+        rounds += 1
+        slots = rng.permutation(n_streams)  # where the windows lie: later entries may lie below the first
+        entries, bad = [], []
+        for i, s in enumerate(streams):
+            total, mo = s.offs[-1], s.model
+            wlen = min(int(rng.choice([0, 1, bs - 1, bs, bs + 1, 3 * bs - 1, int(rng.integers(0, 4 * bs)), total])), total - mo.pos)
+            ends = cu.ends_in_window(s.offs, mo.pos, mo.n_closed, wlen)
+            cap = int(rng.choice([0, 20, 21, big - 1, big, big + 1, 2 * big + 5, int(rng.integers(0, 5 * big)), 1 << 40]))
+            kind = int(rng.integers(0, 12))
+            if kind == 0 and len(ends) >= 2 and ends[0] != ends[-1]:
+                ends = ends[::-1]  # descending: that entry's own S3S_E_INVALID
+                bad.append(i)
+            elif kind == 1:
+                cap = -1
+                bad.append(i)
+            elif kind == 2 and ends:
+                ends = ends[:-1] + [wlen + 1]  # beyond the window
+                bad.append(i)
+            entries.append((i, 1 << 20 | int(slots[i]) << 24, wlen, cap, ends))
+        got, windows = prog.round(entries, streams)
+        batched += windows
+        hosted += len(entries) - len(bad) - windows
+        for (i, _, wlen, cap, ends), g in zip(entries, got):
+            s = streams[i]
+            if i in bad:
+                refused += 1
+                want = cu.Feed(code=-1)
+            else:
+                before = s.model.n_closed
+                want = s.model.feed(wlen, ends, cap)
+                want.sums = [checksum(algo, s.img[s.index[p]:s.index[p + 1]], fresh(algo)) for p in range(before, before + want.parts_closed)]
+            assert (g["code"], g["consumed"], g["out_len"], g["need_src"], g["need_dst"], g["parts_closed"], tuple(g["lengths"])) == want.fields(), \
+                (codec, seed, rounds, i, entries[i], g, want.fields())
+            mo = s.model
+            open_at = s.index[mo.n_closed] if mo.n_closed < len(s.index) - 1 else s.index[-1]
+            carry = checksum(algo, s.img[open_at:open_at + mo.open_img], fresh(algo)) if algo else g["carry"]
+            assert (g["pos"], g["written"], g["open_bytes"], g["open_img"], g["carry"]) == (mo.pos, mo.written, mo.open_bytes, mo.open_img, carry), \
+                (codec, seed, rounds, i, g)
+            if algo and i not in bad:
+                assert g["sums"] == want.sums, (codec, seed, rounds, i, g["sums"], want.sums)
+    prog.close()
+    assert all(s.done for s in streams), "the schedule did not end"
+    return rounds, batched, refused, hosted
