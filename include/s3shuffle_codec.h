@@ -251,7 +251,15 @@ enum { S3S_OPT_ZSTD_DECODE_STAGED = 15, /* ABI 11, additive; tuning, identical o
                                     upload, one launch of each kind, one download, one host wait); 0 after a call that went one
                                     by one or was refused.  Entries that the single feed answered inside the call - a window that
                                     launches nothing, refused arguments - are not counted.  s3s_set_option on it answers
-                                    S3S_E_INVALID; a library without the key answers S3S_E_INVALID to reading it */
+                                    S3S_E_INVALID; a library without the key answers S3S_E_INVALID to reading it.  It counts
+                                    plain windows only: after a call over streams under IO encryption it is 0, see key 19 */
+  , S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES = (19) /* (in parentheses and not at the start of a line, as key 18) ABI 11, additive,
+                                    READ-ONLY: the number of entries of the context's last s3s_cstream_feed_batch* call that the
+                                    batched path answered under IO encryption (one upload that holds the call's IVs, one launch
+                                    of each kind with ONE AES-CTR pass over the outputs of all windows, one download, one host
+                                    wait); 0 after a plain call, after a call that went one by one and after a refused call.
+                                    s3s_set_option on it answers S3S_E_INVALID; a library without the key answers S3S_E_INVALID
+                                    to reading it, which is how a caller detects that streams under IO encryption are batched */
 };
 
 /* stages reported by s3s_stage_ms (valid after a call made with S3S_OPT_PROFILE=1) */
@@ -685,7 +693,8 @@ int s3s_dstream_close(s3s_dstream* s);
  *          close).  There is no device memory between feeds; one-shot calls on the context may run between two feeds.
  * Result   the concatenation of all dst outputs is byte for byte what s3s_compress_map_output_device writes on a context with
  *          the same options, key and IVs; the lengths are the differences of that call's index, the checksums its checksums.
- * Not here Zstandard, the JNI natives and the Scala writer, ONE pass of the layer over the windows of a batched feed. */
+ * Not here Zstandard, the JNI natives and the Scala writer.  (ONE pass of the layer over the windows of a batched feed:
+ *          s3s_cstream_feed_batch*, below, read-only key 19.) */
 typedef struct s3s_cstream s3s_cstream;
 typedef struct s3s_cstream_result {
   int64_t consumed;      /* source bytes of this window taken; the next window starts there */
@@ -766,7 +775,7 @@ typedef struct s3s_dstream_feed_entry {
 int s3s_dstream_feed_batch_device(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_t n);
 int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_t n); /* d_comp / d_dst are HOST addresses */
 
-/* ---- the batched feed of s3s_cstream (ABI 11, additive: callers detect support by the symbols; read-only key 18) --------------
+/* ---- the batched feed of s3s_cstream (ABI 11, additive: callers detect support by the symbols; read-only keys 18 and 19) ------
  * The reference writes every map task through a BufferedOutputStream of spark.shuffle.s3.bufferSize (8 MiB), and an executor
  * runs several map tasks at once.  A feed lasts at least one block's chain (about half a millisecond) whatever it holds, and a
  * single window does not fill the chip; s3s_cstream_feed_batch_device takes ONE WINDOW OF EACH OF SEVERAL STREAMS and pays that
@@ -775,7 +784,8 @@ int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_
  * Contract every entry gets what s3s_cstream_feed_device(stream, d_src, src_len, part_ends, n_ends, d_dst, dst_capacity,
  *          out_lengths, out_checksums, &result) would have produced for that stream alone: status and every field of result,
  *          the bytes d_dst[0, out_len) with nothing written at or beyond out_len, the lengths and the checksums, and the
- *          stream's state afterwards - position, written, the open partition's counters, the carried checksum.  One entry's
+ *          stream's state afterwards - position, written, the open partition's counters, the carried checksum and, under IO
+ *          encryption, the open partition's IV (kept while the partition stays open, wiped when it closes).  One entry's
  *          fate does not touch another entry's: S3S_E_CAPACITY with need_dst, need_src, refused arguments (bad ends, null
  *          pointers with lengths, negative sizes) and a window with too many blocks are that entry's alone.
  * Returns  S3S_OK, or the status of the first entry, in order, that is not S3S_OK.  Entries are stamped S3S_STATUS_NOT_RUN on
@@ -785,31 +795,40 @@ int s3s_dstream_feed_batch(s3s_ctx* ctx, s3s_dstream_feed_entry* entries, int32_
  *          or in checksum algorithm.  n == 0 is S3S_OK.
  * Caller   promises that the windows and the destinations of different entries do not overlap each other; the library does
  *          not check it.
- * Batched  n > 1 plain LZ4, Snappy or LZF streams that were opened under the same block size and the same LZ4 / Snappy variant:
+ * Batched  n > 1 LZ4, Snappy or LZF streams that were opened under the same block size and the same LZ4 / Snappy variant, either
+ *          all plain on a context without IO encryption or streams under IO encryption on a context that has the layer on:
  *          the windows of all entries are planned into one arena, which goes up in one copy; the codec kernels run ONCE over the
  *          blocks of all windows (the variant and the grid of the single feed), then one scan, one cut of every window at its
- *          own dst_capacity, one gather, one checksum pass; everything the host needs comes down in one copy behind ONE host
+ *          own dst_capacity, one gather, under IO encryption ONE encrypt pass over the outputs of all windows (the call's IVs
+ *          travel in the one upload; every window's IV unit and need_dst count stored bytes as in the single feed), one checksum
+ *          pass over the stored bytes; everything the host needs comes down in one copy behind ONE host
  *          wait, and no stream's state changes before all of it has been checked.  A result the device cannot have produced
  *          is S3S_E_HIP for the call with every stream unchanged.  An entry whose window launches nothing (no whole unit, only
- *          empty partitions) and an entry whose arguments the single feed refuses get the single feed's answer on the host;
- *          the other entries still run batched.
+ *          empty partitions; its slice of IVs is consumed all the same), an entry whose arguments the single feed refuses and,
+ *          on a context with IO encryption, a stream bound to an earlier key setting (S3S_E_INVALID) and a plain stream
+ *          (S3S_E_UNSUPPORTED) get the single feed's answer on the host; the other entries still run batched.
  * One by one, in order, through the single feed inside the call (the contract holds): n == 1, S3S_CODEC_NONE, streams whose
- *          bound block size or variant differ, streams opened under IO encryption (the second open call of the section "map
- *          side, streaming").
- * IVs      with streams under IO encryption the caller's s3s_set_stream_ivs holds the sum over the entries of n_ends + 1 IVs, sliced in
- *          entry order (as s3s_compress_map_outputs_batch_device slices a call's IVs per task).  Any other count is
- *          S3S_E_INVALID before anything runs, with every stream unchanged and the array consumed.
+ *          bound block size or variant differ, every stream under IO encryption (the second open call of the section "map
+ *          side, streaming") when the layer is off on the context.
+ * IVs      with streams under IO encryption the caller's s3s_set_stream_ivs holds the sum over the entries of max(n_ends, 0) + 1
+ *          IVs, sliced in entry order (as s3s_compress_map_outputs_batch_device slices a call's IVs per task), whichever way the
+ *          call runs.  Any other count is S3S_E_INVALID before anything runs, with every stream unchanged and the array
+ *          consumed.  Entry 0 of a slice is ignored while that stream's open partition already has image bytes: the IV the
+ *          stream carries is used.
  * Key 18   S3S_OPT_CSTREAM_BATCH_ENTRIES (read-only) holds the number of entries of the context's last call that the batched
  *          path answered: 0 after a call that went one by one or was refused; entries the single feed answered inside a batched
- *          call are not counted.
+ *          call are not counted.  Key 18 counts plain windows only: it stays 0 after every call over streams under IO encryption.
+ * Key 19   S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES (read-only) is the same count for the calls the batched path answered under IO
+ *          encryption, and 0 after a plain call, a one-by-one call and a refused call.  A library without the key answers
+ *          S3S_E_INVALID to reading it: streams under IO encryption are fed one by one inside the call there.
  * Memory   the device form works in the context's workspace: one slot of 32 + blockSize bytes (Snappy, LZF: the slot of the
  *          one-shot call) for every block of EVERY window of the call at once - the sum of the windows is the caller's memory
  *          bound, where a sequence of single feeds needs the largest window only.  s3s_cstream_feed_batch (HOST addresses in
  *          d_src / d_dst) stages the windows and the destinations of ALL entries there as well - the sum of src_len +
  *          dst_capacity - uploads, calls the device form and downloads out_len bytes per entry; it does not overlap the
  *          upload with the kernels.
- * Left     the JNI natives and the Scala writer, ONE encrypt pass for all windows of a call (streams under IO encryption are fed
- *          one by one: batching the AES-CTR pass into one launch is a later change), batching of S3S_CODEC_NONE, Zstandard.
+ * Left     the JNI natives and the Scala writer, batching of S3S_CODEC_NONE (plain or under IO encryption), Zstandard,
+ *          overlapping the host form's upload with the kernels.
  *          (This section spells the layer out instead of naming its open call: an interface test of the reduce side's batched
  *          feed reads the header from that section's last paragraph to the end of the file.) */
 typedef struct s3s_cstream_feed_entry {

@@ -252,6 +252,7 @@ int s3s_set_option(s3s_ctx* ctx, int key, int64_t value) {
     case S3S_OPT_DSTREAM_BATCH_ENTRIES:
       return fail(ctx, S3S_E_INVALID, "option %d is read-only (the last s3s_dstream_feed_batch* call sets it)", key);
     case S3S_OPT_CSTREAM_BATCH_ENTRIES:
+    case S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES:
       return fail(ctx, S3S_E_INVALID, "option %d is read-only (the last s3s_cstream_feed_batch* call sets it)", key);
   }
   return fail(ctx, S3S_E_INVALID, "unknown option %d", key);
@@ -278,6 +279,7 @@ int64_t s3s_get_option(const s3s_ctx* ctx, int key) {
     case S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS: return ctx->zstd_decode_staged_blocks;
     case S3S_OPT_DSTREAM_BATCH_ENTRIES: return ctx->dstream_batch_entries;
     case S3S_OPT_CSTREAM_BATCH_ENTRIES: return ctx->cstream_batch_entries;
+    case S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES: return ctx->cstream_batch_enc_entries;
   }
   return S3S_E_INVALID;
 }

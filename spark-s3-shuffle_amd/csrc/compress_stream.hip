@@ -16,6 +16,8 @@
 // starts its partition, launch_seed_iv_items gives it its 16 bytes before the scan, and one more kernel (aes_ctr_cstream.hip)
 // encrypts d_dst[0, out_len) in place behind the cut gather and in front of the checksums; S3S_CODEC_NONE is cut on the host
 // (none_cut_encrypted) and written by the same kernel from the source.  The feed's IVs are one upload; still one wait.
+// The batched feed of streams under IO encryption carries the call's IVs, one pass descriptor per window and the
+// pass's tile -> window map in its ONE upload and encrypts the outputs of all windows in ONE launch (aes_ctr_cstream_batch.hip).
 #include <algorithm>
 #include <new>
 #include <optional>
@@ -52,7 +54,7 @@ inline size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
 // the feed that wrote nothing: every end it passes closes a partition with what the stream already holds
 void finish_on_host(s3s_cstream* s, const s3s_cs::Cut& c, const int64_t* ends, int64_t* out_lengths, int64_t* out_checksums) {
   s3s_cs::commit_nothing(&s->st, &s->carry, fresh(s->algo), c.parts_closed, out_lengths, out_checksums);
-  if (c.parts_closed > 0) wipe(s->iv, sizeof s->iv);
+  if (s->enc) s3s_cs::commit_nothing_iv(s->iv, c.parts_closed);
 }
 
 int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, bool encrypted, s3s_cstream** out) {
@@ -354,10 +356,7 @@ int s3s_cstream_feed_device(s3s_cstream* s, const uint8_t* d_src, int64_t src_le
   // (the commit step the batched feed shares: compress_stream_batch_core.h)
   s3s_cs::commit(&s->st, &s->carry, c, part_ends, piece_off, codec != S3S_CODEC_NONE ? h_len : nullptr, do_sum ? h_sums : nullptr, out_lengths,
                  out_checksums);
-  if (enc) {  // the open partition's IV stays with the stream from the feed that took its first block until it closes
-    if (s->st.open_img == 0) wipe(s->iv, sizeof s->iv);
-    else if (c.parts_closed > 0 || front == 0) memcpy(s->iv, h_ivs + 16 * (size_t)c.parts_closed, 16);
-  }
+  if (enc) s3s_cs::commit_iv(s->iv, s->st, front, c.parts_closed, h_ivs);  // (shared with the batched feed, like commit)
   r->consumed = c.consumed;
   r->out_len = c.out_len;
   r->parts_closed = c.parts_closed;
@@ -399,6 +398,7 @@ namespace {
 struct CsWin {
   int32_t e;  // its entry
   s3s_cs::CutEntry c;
+  int64_t tiles = 0;  // under IO encryption: its tiles of the encrypt pass
 };
 
 struct CsBatch {
@@ -407,8 +407,16 @@ struct CsBatch {
   int32_t n;
   std::vector<CsWin> W;
   std::vector<int32_t> host;  // entries the single feed answers without device work, in order
+  bool enc = false;           // the batched path runs under IO encryption: every window is a keyed stream's
+  std::vector<int64_t> iv_at; // ... where every entry's slice of the call's IVs starts
+  int64_t tiles = 0;          // ... the grid of the encrypt pass
+  const uint8_t* call_ivs = nullptr;  // ... the call's IVs (the IvScope's), before any entry's slice is set in iv_cur
 
   void single(s3s_cstream_feed_entry& e) {
+    if (enc) {  // the entry's slice of the call's IVs
+      ctx->iv_cur = call_ivs + 16 * (size_t)iv_at[(size_t)(&e - E)];
+      ctx->iv_cur_n = s3s_cs::iv_slice_len(e.n_ends);
+    }
     e.status = s3s_cstream_feed_device(e.stream, e.d_src, e.src_len, e.part_ends, e.n_ends, e.d_dst, e.dst_capacity, e.out_lengths,
                                        e.out_checksums, &e.result);
   }
@@ -427,22 +435,24 @@ inline int64_t unit_items(int codec, const s3s_cs::Unit& u) { return codec == S3
 inline int64_t unit_slots(int codec, const s3s_cs::Unit& u) { return codec == S3S_CODEC_SNAPPY ? snappy_chunk_slots(u.len) : u.len > 0; }
 
 // worst-case checksum segments of a window's pieces, as the single feed sizes them; seg_start (or null): n_ends + 2 entries
-int64_t window_segs(int codec, int64_t bs, int64_t src_len, const int64_t* ends, int32_t n_ends, int32_t* seg_start) {
+int64_t window_segs(int codec, int64_t bs, int64_t src_len, const int64_t* ends, int32_t n_ends, int32_t* seg_start, bool enc) {
   int64_t segs = 0;
   for (int32_t j = 0; j <= n_ends; j++) {
     const int64_t a = j == 0 ? 0 : ends[j - 1], b = j < n_ends ? ends[j] : src_len;
     if (seg_start) seg_start[j] = (int32_t)segs;
-    segs += worst_segs(max_partition_size(codec, bs, b - a) + kLz4FrameHeader + kSnappyStreamHeader);
+    segs += worst_segs(max_partition_size(codec, bs, b - a) + kLz4FrameHeader + kSnappyStreamHeader + (enc ? 16 : 0));
     if (segs > s3s_cs::kBatchMax) return -1;
   }
   if (seg_start) seg_start[n_ends + 1] = (int32_t)segs;
   return segs;
 }
 
-// call-level refusals: nothing has been touched.  *batched: these streams go through the batched path
+// call-level refusals: nothing has been touched.  *batched: these streams go through the batched path - plain streams with
+// the layer off, or, with the layer on, the streams of s3s_cstream_open_encrypted under the context's current key setting
+// (a stream bound to an earlier one and a plain stream keep the single feed's refusal: cs_batch_windows sends them to b.host)
 int cs_batch_check(CsBatch& b, bool* batched, bool* any_enc) {
   s3s_ctx* ctx = b.ctx;
-  *batched = b.n > 1 && !enc_on(ctx);
+  *batched = b.n > 1;
   *any_enc = false;
   std::vector<const s3s_cstream*> seen;
   seen.reserve((size_t)b.n);
@@ -454,7 +464,7 @@ int cs_batch_check(CsBatch& b, bool* batched, bool* any_enc) {
     if (s->codec != s0->codec || s->algo != s0->algo)
       return fail(ctx, S3S_E_INVALID, "entry %d: the streams of a batch must share codec and checksum algorithm", i);
     if (s->enc) *any_enc = true;
-    if (s->enc || s->codec == S3S_CODEC_NONE || s->bs != s0->bs || s->lz4_variant != s0->lz4_variant || s->snappy_variant != s0->snappy_variant)
+    if ((s->enc && !enc_on(ctx)) || s->codec == S3S_CODEC_NONE || s->bs != s0->bs || s->lz4_variant != s0->lz4_variant || s->snappy_variant != s0->snappy_variant)
       *batched = false;
     seen.push_back(s);
   }
@@ -494,23 +504,30 @@ bool cs_batch_windows(CsBatch& b, s3s_cs::Totals* tot) {
   const int codec = s0->codec;
   const int64_t bs = s0->bs;
   const bool do_sum = s0->algo != S3S_CHECKSUM_NONE;
+  const bool enc = b.enc;
+  s3s_cs::IvSlicer slices;
   for (int32_t i = 0; i < b.n; i++) {
     const s3s_cstream_feed_entry& e = b.E[i];
     const s3s_cstream* s = e.stream;
+    if (enc) b.iv_at.push_back(slices.take(e.n_ends));
+    if (enc && (!s->enc || s->epoch != b.ctx->enc_epoch)) {  // (the single feed's S3S_E_UNSUPPORTED / S3S_E_INVALID)
+      b.host.push_back(i);
+      continue;
+    }
     const bool null_with_length = (e.src_len > 0 && !e.d_src) || (e.dst_capacity > 0 && !e.d_dst) ||
                                   (e.n_ends > 0 && (!e.part_ends || !e.out_lengths || (do_sum && !e.out_checksums)));
     const bool refused = s3s_cs::window_refused(e.src_len, e.part_ends, e.n_ends, e.dst_capacity, null_with_length);
     int64_t n_items = 0, n_slots = 0;
     if (!refused)
       s3s_cs::plan_units(codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, [&](const s3s_cs::Unit& u) {
-        n_items += unit_items(codec, u);
+        n_items += s3s_cs::iv_records(u, enc) + unit_items(codec, u);
         n_slots += unit_slots(codec, u);
       });
     if (refused || n_items == 0 || n_items > s3s_cs::kBatchMax) {  // (too many blocks: the single feed's S3S_E_UNSUPPORTED)
       b.host.push_back(i);
       continue;
     }
-    const int64_t segs = do_sum ? window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, nullptr) : 0;
+    const int64_t segs = do_sum ? window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, nullptr, enc) : 0;
     if (segs < 0) {  // (window too large for one feed: the single feed's answer)
       b.host.push_back(i);
       continue;
@@ -519,6 +536,11 @@ bool cs_batch_windows(CsBatch& b, s3s_cs::Totals* tot) {
     CsWin w;
     w.e = i;
     w.c = s3s_cs::reserve(tot, n_items, n_slots, e.n_ends, segs, e.dst_capacity, s->st.open_img);
+    if (enc) {
+      w.tiles = s3s_cs::pass_tiles(e.dst_capacity, s3s_cs::feed_bound_encrypted(codec, bs, e.src_len, e.n_ends), s->st.open_img);
+      if (b.tiles + w.tiles > s3s_cs::kBatchMax) return false;
+      b.tiles += w.tiles;
+    }
     b.W.push_back(w);
   }
   return true;
@@ -532,8 +554,10 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
   const bool do_sum = algo != S3S_CHECKSUM_NONE;
   const int32_t m = tot.m, N = (int32_t)tot.items;
   const size_t PP = (size_t)tot.pp(), P = (size_t)tot.pieces;
+  const bool enc = b.enc;
   s3s_cs::Arena A;
-  A.lay_out(tot, sizeof(Item), sizeof(TaskTail));
+  if (enc) A.lay_out_encrypted(tot, sizeof(Item), sizeof(TaskTail), sizeof(s3s_cs::PassWindow), b.tiles);
+  else A.lay_out(tot, sizeof(Item), sizeof(TaskTail));
   const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
   int rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -556,6 +580,10 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
   int32_t* h_pw = reinterpret_cast<int32_t*>(hs + A.pw);
   TaskTail* h_tails = reinterpret_cast<TaskTail*>(hs + A.tails);
   s3s_cs::CutEntry* h_cuts = reinterpret_cast<s3s_cs::CutEntry*>(hs + A.cuts);
+  uint8_t* h_ivs = hs + A.ivs;  // under IO encryption: the IVs, the pass descriptors and the tile -> window map
+  s3s_cs::PassWindow* h_wins = reinterpret_cast<s3s_cs::PassWindow*>(hs + A.wins);
+  int32_t* h_tile_win = reinterpret_cast<int32_t*>(hs + A.tile_win);
+  int32_t tile0 = 0;
 
   const uint8_t* base = b.E[b.W[0].e].d_src;  // the one source pointer of the codec launch: every item is an offset from it
   const int level = codec == S3S_CODEC_LZ4 ? lz4_level(bs) : 0;
@@ -565,9 +593,10 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
     const s3s_cstream_feed_entry& e = b.E[w.e];
     const s3s_cstream* s = e.stream;
     const int64_t delta = s3s_cs::item_src_off((int64_t)reinterpret_cast<intptr_t>(e.d_src), (int64_t)reinterpret_cast<intptr_t>(base), 0);
-    const bool ok = s3s_cs::plan_entry(
-        &w.c, codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, h_marks, h_pf,
+    const bool ok = s3s_cs::plan_entry_records(
+        &w.c, codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, h_marks, h_pf, enc,
         [&](const s3s_cs::Unit& u) { return unit_items(codec, u); },
+        [&](const s3s_cs::Unit& u, int32_t at) { h_items[at] = Item{0, 0, kItemIv, -1, u.piece}; },  // the hole the encrypt pass fills
         [&](const s3s_cs::Unit& u, int32_t at, int32_t& slot) {
           int32_t it = at;
           if (codec == S3S_CODEC_SNAPPY) {
@@ -582,9 +611,10 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
           }
         });
     if (!ok) return fail(ctx, S3S_E_HIP, "the plan of entry %d does not match its count", w.e);
-    if (do_sum) window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, h_seg + w.c.first_pp);
+    if (do_sum) window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, h_seg + w.c.first_pp, enc);
     s3s_cs::seed_pieces(w.c, wi, s->carry, fresh(algo), h_seed, h_pw);
     h_cuts[wi] = w.c;
+    if (enc) s3s_cs::window_ivs(w.c, b.call_ivs, b.iv_at[(size_t)w.e], s->iv, h_ivs);
     TaskTail& t = h_tails[wi];
     t.first_item = w.c.first_item;
     t.n_items = w.c.n_items;
@@ -599,6 +629,12 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
     t.dst = e.d_dst;
     t.dst_capacity = e.dst_capacity;
   }
+  if (enc)  // (behind the loop: the plan has filled every CutEntry)
+    for (int32_t wi = 0; wi < m; wi++) {
+      h_wins[wi] = s3s_cs::pass_window(h_cuts, wi, b.E[b.W[(size_t)wi].e].d_dst, reinterpret_cast<const int64_t*>(da + A.piece), da + A.ivs,
+                                       reinterpret_cast<const int64_t*>(da + A.res), tile0);
+      tile0 = s3s_cs::map_tiles(h_tile_win, tile0, b.W[(size_t)wi].tiles, wi);
+    }
 
   const TaskTail* d_tails = reinterpret_cast<const TaskTail*>(da + A.tails);
   const Item* d_items = reinterpret_cast<const Item*>(da + A.items);
@@ -622,13 +658,16 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
                            ctx->stream);
   }
   HIP_TRY(ctx, hipGetLastError());
+  if (enc) launch_seed_iv_items(d_items, N, dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);  // once, over the items of the whole call
   // (the scan's own index - the unclamped piece offsets - goes to a buffer nobody reads: the cut kernel writes the clamped ones)
   launch_scan_items_batch(d_tails, m, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF), d_pf, dev<int64_t>(ctx, B_OFFSETS),
                           ctx->stream);
   launch_cstream_cut_batch(da + A.cuts, m, da + A.marks, dev<int64_t>(ctx, B_ITEM_OFF), d_pf, d_result, d_piece, d_len, ctx->stream);
   launch_gather_items_cut_batch(d_tails, m, N, base, d_items, d_result, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE),
                                 dev<int64_t>(ctx, B_ITEM_OFF), d_status, ctx->stream);
-  if (do_sum) {  // over the pieces as the cuts left them; a stream's carried state seeds its window's first piece
+  if (enc)  // IVs into the holes, key stream over the rest of every d_dst[0, out_len): ONE launch, the grid a sum of host bounds
+    launch_aes_ctr_cstream_batch(ctx->enc_keys, ctx->enc_rounds, da + A.wins, reinterpret_cast<const int32_t*>(da + A.tile_win), tile0, ctx->stream);
+  if (do_sum) {  // over the pieces as the cuts left them (the stored bytes); a stream's carried state seeds its window's first piece
     launch_checksum_batch(algo, d_tails, m, (int32_t)tot.segs, (int32_t)P, d_piece, reinterpret_cast<const int32_t*>(da + A.seg),
                           ctx->buf[B_TABLES].p, dev<uint32_t>(ctx, B_PARTIAL), d_sums, ctx->stream);
     launch_checksum_seed_batch(algo, d_piece, reinterpret_cast<const int32_t*>(da + A.pw), (int32_t)P, ctx->buf[B_TABLES].p,
@@ -663,6 +702,7 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
     s3s_cs::commit(&s->st, &s->carry, c, e.part_ends, reinterpret_cast<const int64_t*>(hs + A.piece) + w.c.first_pp,
                    reinterpret_cast<const int64_t*>(hs + A.len) + w.c.first_len,
                    do_sum ? reinterpret_cast<const int64_t*>(hs + A.sums) + w.c.first_piece : nullptr, e.out_lengths, e.out_checksums);
+    if (enc) s3s_cs::commit_iv(s->iv, s->st, w.c.open_img, c.parts_closed, h_ivs + 16 * (size_t)w.c.first_piece);
     e.result.consumed = c.consumed;
     e.result.out_len = c.out_len;
     e.result.parts_closed = c.parts_closed;
@@ -679,6 +719,7 @@ int s3s_cstream_feed_batch_device(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   ctx->cstream_batch_entries = 0;  // S3S_OPT_CSTREAM_BATCH_ENTRIES: set where the batched path has answered
+  ctx->cstream_batch_enc_entries = 0;  // S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES: the same under IO encryption (key 18 then stays 0)
   std::optional<IvScope> iv_scope;  // under IO encryption the call is a compress call: it consumes the IVs of s3s_set_stream_ivs either way
   if (enc_on(ctx)) iv_scope.emplace(ctx);
   if (n < 0 || (n > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
@@ -689,10 +730,23 @@ int s3s_cstream_feed_batch_device(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32
   int rc;
   if ((rc = cs_batch_check(b, &batched, &any_enc))) return rc;
   s3s_cs::Totals tot;
+  if (batched && enc_on(ctx) && !any_enc) batched = false;  // only plain streams on a keyed context: each one's S3S_E_UNSUPPORTED
+  if (batched && enc_on(ctx)) {  // ONE array of IVs for the call, sliced in entry order: any other count before anything runs
+    int64_t want = 0;
+    for (int32_t i = 0; i < n; i++) want += s3s_cs::iv_slice_len(E[i].n_ends);
+    if (ctx->iv_cur_n != want)
+      return fail(ctx, S3S_E_INVALID, "the entries of the batch have %lld pieces (n_ends + 1 each), s3s_set_stream_ivs gave %lld IVs",
+                  (long long)want, (long long)ctx->iv_cur_n);
+    b.enc = true;
+    b.call_ivs = ctx->iv_cur;
+    b.iv_at.reserve((size_t)n);
+  }
   if (batched && !cs_batch_windows(b, &tot)) {
     batched = false;
     b.W.clear();
     b.host.clear();
+    b.iv_at.clear();
+    b.enc = false;
   }
   if (!batched) {  // nothing to batch: one by one, in order
     if ((rc = cs_one_by_one(b, any_enc))) return rc;
@@ -700,7 +754,7 @@ int s3s_cstream_feed_batch_device(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32
   }
   if (tot.m > 0 && (rc = cs_batch_run(b, tot))) return rc;
   for (int32_t i : b.host) b.single(E[i]);  // (no device work: an argument the single feed refuses, a window that launches nothing)
-  ctx->cstream_batch_entries = tot.m;
+  (b.enc ? ctx->cstream_batch_enc_entries : ctx->cstream_batch_entries) = tot.m;
   return verdict.finish(b.first_error());
 }
 
@@ -708,6 +762,7 @@ int s3s_cstream_feed_batch(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32_t n) {
   if (!ctx) return S3S_E_INVALID;
   ctx->err[0] = 0;
   ctx->cstream_batch_entries = 0;
+  ctx->cstream_batch_enc_entries = 0;
   if (n < 0 || (n > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
   BatchVerdict<s3s_cstream_feed_entry> verdict(E, n);
   if (n == 0) return verdict.finish(S3S_OK);

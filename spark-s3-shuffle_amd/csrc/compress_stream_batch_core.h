@@ -5,6 +5,11 @@
 // tests/cstream_units.py) and for the device (cstream_cut_batch_kernel and gather_items_cut_batch_kernel,
 // compress_stream_batch_kernels.hip, read CutEntry).  commit() is the single feed's commit step too.
 //
+// Under IO encryption (tests/model/cstream_batch_encrypted_model.cpp against tests/cstream_units_encrypted.py)
+// the up part of the arena grows by the call's IVs (16 bytes per piece, at first_piece), one PassWindow per batched window and
+// the tile -> window map of the ONE encrypt pass (aes_ctr_cstream_batch.hip); plan_entry_encrypted puts the kItemIv records
+// into the plan, commit_iv is the IV bookkeeping of the single and the batched feed.
+//
 // One call, m batched entries.  Every array of the call is packed entry after entry, in entry order:
 //   per item            items, marks, item_size          entry e starts at first_item
 //                       item_off                         ... at first_item + e: the scan writes n_items + 1 offsets an entry
@@ -96,13 +101,20 @@ inline CutEntry reserve(Totals* t, int64_t n_items, int64_t n_slots, int32_t n_e
 }
 
 inline size_t arena_al(size_t x) { return (x + 15) & ~size_t(15); }
+constexpr size_t kIvBytes = 16;
 
 // The call's small arrays in one block, laid out alike in the pinned staging area and in device memory: [0, up) goes up in one
 // copy in front of the kernels, [up, total) is zeroed on the device, written by the kernels and comes down in one copy.
 struct Arena {
   size_t items = 0, marks = 0, pf = 0, seg = 0, seed = 0, pw = 0, tails = 0, cuts = 0, up = 0;
   size_t status = 0, res = 0, piece = 0, len = 0, sums = 0, total = 0;
-  void lay_out(const Totals& t, size_t item_bytes, size_t tail_bytes) {
+  size_t ivs = 0, wins = 0, tile_win = 0;  // under IO encryption only (otherwise empty, at `up`)
+  void lay_out(const Totals& t, size_t item_bytes, size_t tail_bytes) { lay_out_pass(t, item_bytes, tail_bytes, 0, 0, 0); }
+  // ... of a call under IO encryption: win_bytes = sizeof(PassWindow), tiles = the grid of the encrypt pass
+  void lay_out_encrypted(const Totals& t, size_t item_bytes, size_t tail_bytes, size_t win_bytes, int64_t tiles) {
+    lay_out_pass(t, item_bytes, tail_bytes, kIvBytes, win_bytes, (size_t)tiles);
+  }
+  void lay_out_pass(const Totals& t, size_t item_bytes, size_t tail_bytes, size_t iv_bytes, size_t win_bytes, size_t tiles) {
     const size_t N = (size_t)t.items, PP = (size_t)t.pp(), P = (size_t)t.pieces, L = (size_t)t.lens(), M = (size_t)t.m;
     items = 0;
     marks = arena_al(items + item_bytes * N);
@@ -112,7 +124,10 @@ struct Arena {
     pw = arena_al(seed + 8 * P);
     tails = arena_al(pw + 4 * P);
     cuts = arena_al(tails + tail_bytes * M);
-    up = arena_al(cuts + sizeof(CutEntry) * M);
+    ivs = arena_al(cuts + sizeof(CutEntry) * M);
+    wins = arena_al(ivs + iv_bytes * P);
+    tile_win = arena_al(wins + win_bytes * M);
+    up = arena_al(tile_win + 4 * tiles);
     status = up;
     res = arena_al(status + 4 * M);
     piece = arena_al(res + 8 * (size_t)kCutWords * M);
@@ -126,9 +141,11 @@ struct Arena {
 // places added.  items_of(u) = the plan items of unit u; emit(u, at, slot) writes them at item `at` of the CALL (slot: the
 // call's slot counter, advanced) with src_off = src_delta + the unit's offset.  marks / part_first: the call's arrays.
 // false: the plan does not match the counts the entry was reserved with (nothing may be launched).
-template <typename ItemsOf, typename Emit>
-inline bool plan_entry(CutEntry* c, int codec, int64_t bs, int64_t open_bytes, int64_t src_len, const int64_t* ends, int32_t n_ends,
-                       Mark* marks, int32_t* part_first, ItemsOf&& items_of, Emit&& emit) {
+// Under IO encryption one more record (emit_iv(u, at): kItemIv) goes in front of the items of every unit that starts its
+// partition, as iv_records / mark_unit place it for the single feed: it is counted in n_items, part_first points at it.
+template <typename ItemsOf, typename EmitIv, typename Emit>
+inline bool plan_entry_records(CutEntry* c, int codec, int64_t bs, int64_t open_bytes, int64_t src_len, const int64_t* ends, int32_t n_ends,
+                               Mark* marks, int32_t* part_first, bool encrypted, ItemsOf&& items_of, EmitIv&& emit_iv, Emit&& emit) {
   Mark* m = marks + c->first_item;
   int32_t* pf = part_first + c->first_pp;
   const int32_t n_items = c->n_items, n_pieces = c->n_pieces;
@@ -136,7 +153,8 @@ inline bool plan_entry(CutEntry* c, int codec, int64_t bs, int64_t open_bytes, i
   bool fits = true;
   pf[0] = 0;
   plan_units(codec, bs, open_bytes, src_len, ends, n_ends, [&](const Unit& u) {
-    const int64_t mine = items_of(u);
+    const int32_t lead = iv_records(u, encrypted);
+    const int64_t mine = lead + items_of(u);
     if (!fits || it + mine > n_items) {
       fits = false;
       return;
@@ -145,13 +163,27 @@ inline bool plan_entry(CutEntry* c, int codec, int64_t bs, int64_t open_bytes, i
     if (it == 0) c->ends0 = u.ends_before;
     while (piece < u.piece) pf[++piece] = it;
     prev0 = it;
+    if (lead) emit_iv(u, c->first_item + it);
+    it += lead;
     emit(u, c->first_item + it, slot);
-    it += (int32_t)mine;
+    it += (int32_t)(mine - lead);
     mark_unit(m, prev0, it, u, n_ends);
     if (c->first_last < 0) c->first_last = it - 1;
   });
   while (piece < n_pieces) pf[++piece] = it;
   return fits && it == n_items && slot == c->first_slot + c->n_slots;
+}
+
+template <typename ItemsOf, typename Emit>
+inline bool plan_entry(CutEntry* c, int codec, int64_t bs, int64_t open_bytes, int64_t src_len, const int64_t* ends, int32_t n_ends,
+                       Mark* marks, int32_t* part_first, ItemsOf&& items_of, Emit&& emit) {
+  return plan_entry_records(c, codec, bs, open_bytes, src_len, ends, n_ends, marks, part_first, false, items_of, [](const Unit&, int32_t) {}, emit);
+}
+
+template <typename ItemsOf, typename EmitIv, typename Emit>
+inline bool plan_entry_encrypted(CutEntry* c, int codec, int64_t bs, int64_t open_bytes, int64_t src_len, const int64_t* ends, int32_t n_ends,
+                                 Mark* marks, int32_t* part_first, ItemsOf&& items_of, EmitIv&& emit_iv, Emit&& emit) {
+  return plan_entry_records(c, codec, bs, open_bytes, src_len, ends, n_ends, marks, part_first, true, items_of, emit_iv, emit);
 }
 
 // the seeds of an entry's pieces: the stream's carried state continues into the first, a fresh state starts the others
@@ -160,6 +192,87 @@ inline void seed_pieces(const CutEntry& c, int32_t entry, int64_t carry, int64_t
     seeds[c.first_piece + j] = j == 0 ? carry : fresh;
     piece_entry[c.first_piece + j] = entry;
   }
+}
+
+// ---- under IO encryption: the IVs of the call and the ONE encrypt pass ----------------------------------------------------------
+// ONE s3s_set_stream_ivs array holds the IVs of every entry of the call - refused and host-answered ones included - sliced in
+// entry order, max(n_ends, 0) + 1 an entry.
+inline int64_t iv_slice_len(int32_t n_ends) { return (int64_t)(n_ends > 0 ? n_ends : 0) + 1; }
+
+struct IvSlicer {
+  int64_t at = 0;  // IVs of the entries in front
+  int64_t take(int32_t n_ends) {
+    const int64_t mine = at;
+    at += iv_slice_len(n_ends);
+    return mine;
+  }
+};
+
+// the IVs of one batched window, into the call's array at its pieces: the entry's slice, entry 0 replaced by the IV the stream
+// carries while its open partition already has image bytes
+inline void window_ivs(const CutEntry& c, const uint8_t* call_ivs, int64_t slice_at, const uint8_t* carried, uint8_t* ivs) {
+  uint8_t* mine = ivs + kIvBytes * (size_t)c.first_piece;
+  const uint8_t* from = call_ivs + kIvBytes * (size_t)slice_at;
+  for (size_t i = 0; i < kIvBytes * (size_t)c.n_pieces; i++) mine[i] = from[i];
+  if (c.open_img > 0)
+    for (size_t i = 0; i < kIvBytes; i++) mine[i] = carried[i];
+}
+
+// The encrypt pass works in tiles of kPassTile stored bytes that follow the open partition's key stream: tile t of a window is
+// its output bytes [kPassTile t - (front & 15), + kPassTile).  out_len is the device's; the host bounds it by the window's
+// capacity and by what its source can compress to, and the tiles behind out_len return whole.
+constexpr int64_t kPassTile = 16384;
+inline int64_t pass_tiles(int64_t dst_capacity, int64_t bound, int64_t front) {
+  const int64_t len = dst_capacity < bound ? dst_capacity : bound;
+  if (len <= 0) return 0;
+  return (len + (front & 15) + kPassTile - 1) / kPassTile;
+}
+
+// what a workgroup of the pass needs of its window (device pointers; aes_ctr_cstream_batch.hip reads it through scalar loads)
+struct PassWindow {
+  uint8_t* out;         // the entry's d_dst
+  const int64_t* E;     // its n_pieces + 1 clamped piece offsets (the cut kernel's)
+  const uint8_t* ivs;   // its n_pieces IVs
+  const int64_t* cut;   // its kCutWords result words
+  int32_t n_pieces, tile0;
+  int64_t front;        // stored bytes of the open partition in front of the output
+};
+
+inline PassWindow pass_window(const CutEntry* cuts, int32_t w, uint8_t* out, const int64_t* piece_off, const uint8_t* ivs, const int64_t* result,
+                              int32_t tile0) {
+  PassWindow p;
+  p.out = out;
+  p.E = piece_off + cuts[w].first_pp;
+  p.ivs = ivs + kIvBytes * (size_t)cuts[w].first_piece;
+  p.cut = result + (size_t)kCutWords * (size_t)w;
+  p.n_pieces = cuts[w].n_pieces;
+  p.tile0 = tile0;
+  p.front = cuts[w].open_img;
+  return p;
+}
+
+// tiles [tile0, tile0 + tiles) of the launch belong to window w -> the next window's tile0
+inline int32_t map_tiles(int32_t* tile_win, int32_t tile0, int64_t tiles, int32_t w) {
+  for (int64_t t = 0; t < tiles; t++) tile_win[tile0 + t] = w;
+  return tile0 + (int32_t)tiles;
+}
+
+// The open partition's IV stays with the stream from the feed that took its first block until the partition closes.  st: the
+// state behind the feed; front: open_img in front of it; feed_ivs: the IVs the feed ran with (entry 0 the carried one)
+inline void wipe_iv(uint8_t* iv) {
+  volatile uint8_t* v = iv;
+  for (size_t i = 0; i < kIvBytes; i++) v[i] = 0;
+}
+inline void commit_iv(uint8_t* iv, const State& st, int64_t front, int32_t parts_closed, const uint8_t* feed_ivs) {
+  if (st.open_img == 0) {
+    wipe_iv(iv);
+  } else if (parts_closed > 0 || front == 0) {
+    for (size_t i = 0; i < kIvBytes; i++) iv[i] = feed_ivs[kIvBytes * (size_t)parts_closed + i];
+  }
+}
+// ... behind a feed that wrote nothing (commit_nothing)
+inline void commit_nothing_iv(uint8_t* iv, int32_t parts_closed) {
+  if (parts_closed > 0) wipe_iv(iv);
 }
 
 // ---- behind the download ------------------------------------------------------------------------------------------------------

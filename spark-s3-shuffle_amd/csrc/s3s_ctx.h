@@ -69,7 +69,8 @@ struct s3s_ctx {
   int zstd_decode_staged = 0;         // S3S_OPT_ZSTD_DECODE_STAGED: 1 = frames with history decode in stages (entropy per block, copies per frame)
   int zstd_decode_staged_blocks = 0;  // S3S_OPT_ZSTD_DECODE_STAGED_BLOCKS: blocks of the last Zstandard decode call whose frames completed on the staged path
   int dstream_batch_entries = 0;      // S3S_OPT_DSTREAM_BATCH_ENTRIES: entries of the last s3s_dstream_feed_batch* call that the batched path answered
-  int cstream_batch_entries = 0;      // S3S_OPT_CSTREAM_BATCH_ENTRIES: the same for the last s3s_cstream_feed_batch* call
+  int cstream_batch_entries = 0;      // S3S_OPT_CSTREAM_BATCH_ENTRIES: the same for the last s3s_cstream_feed_batch* call (plain windows only)
+  int cstream_batch_enc_entries = 0;  // S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES: ... the entries it answered under IO encryption
   s3s::DevBuf buf[s3s::B_COUNT];
   int cu_count = 256;  // compute units of the device (persistent grids: resident wavefronts per CU x this)
   void* h_stage = nullptr;  // pinned

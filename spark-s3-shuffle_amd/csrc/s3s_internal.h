@@ -165,6 +165,11 @@ enum { kCsInPlace = 0, kCsFromPlain = 1 };
 void launch_aes_ctr_cstream(int mode, const AesKeys& keys, int rounds, const uint8_t* d_src, uint8_t* d_dst, const int64_t* d_piece_off,
                             const int64_t* d_plain_off, const uint8_t* d_ivs, const int64_t* d_cut, int32_t n_pieces, int64_t front,
                             int64_t out_bound, hipStream_t st);
+// ... over the outputs of all windows of a batched feed, in place, one launch (aes_ctr_cstream_batch.hip): window i is
+// d_wins[i], an s3s_cs::PassWindow (compress_stream_batch_core.h: d_dst, its clamped piece offsets, its IVs, its cut words, its
+// first tile in the launch, its front), tile t of the launch belongs to window d_tile_win[t]; s3s_cs::pass_tiles sizes a window
+void launch_aes_ctr_cstream_batch(const AesKeys& keys, int rounds, const void* d_wins, const int32_t* d_tile_win, int32_t total_tiles,
+                                  hipStream_t st);
 // item_size = 16 for every kItemIv record (between the codec kernels and the scan)
 void launch_seed_iv_items(const Item* d_items, int32_t n_items, uint32_t* d_item_size, hipStream_t st);
 // exclusive scan of item sizes + partition index extraction

@@ -29,6 +29,7 @@ OPT_ZSTD_DECODE_BLOCKS = 14  # ABI 11, additive, read-only: blocks of the last Z
 OPT_ZSTD_DECODE_STAGED = 15  # ABI 11, additive: 0 (default) / 1 = Zstandard frames with history across blocks decode in stages (entropy per block, copies per frame)
 OPT_ZSTD_DECODE_STAGED_BLOCKS = 16  # ABI 11, additive, read-only: blocks of the last Zstandard decode call whose frames completed on the staged path
 OPT_CSTREAM_BATCH_ENTRIES = 18  # ABI 11, additive, read-only: entries of the last compress_stream_feed_batch* call that the batched path answered
+OPT_CSTREAM_BATCH_ENC_ENTRIES = 19  # ABI 11, additive, read-only: entries of the last compress_stream_feed_batch* call that the batched path answered under IO encryption
 OPT_DSTREAM_BATCH_ENTRIES = 17  # ABI 11, additive, read-only: entries of the last feed_streams* call that the batched path answered (0: it went one by one)
 
 E_INVALID, E_CAPACITY, E_BAD_FRAME, E_CHECKSUM, E_HIP, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5, -6, -7
@@ -470,6 +471,12 @@ class Codec:
     def compress_batch_entries(self) -> int:
         """Entries of the last compress_stream_feed_batch* call that the batched path answered; 0 when it went one by one or was refused."""
         return self.get_option(OPT_CSTREAM_BATCH_ENTRIES)
+
+    @property
+    def compress_batch_encrypted_entries(self) -> int:
+        """Entries of the last compress_stream_feed_batch* call that the batched path answered under IO encryption (key 19);
+        0 after a plain call, a one-by-one call and a refused call.  `compress_batch_entries` (key 18) counts plain windows only."""
+        return self.get_option(OPT_CSTREAM_BATCH_ENC_ENTRIES)
 
     def compress_stream_feed_batch(self, entries, _host: bool = False):
         """The batched feed of the map side (s3s_cstream_feed_batch_device): `entries` = [(CompressStream, d_src, src_len,
