@@ -469,19 +469,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
         if (codec == S3S_CODEC_ZSTD) h_items[it++] = Item{u, 0, kItemZstdHeader, -1, p};
         for (int64_t pos = 0; pos < u; pos += bs) {
           const int32_t len = (int32_t)((u - pos) < bs ? (u - pos) : bs);
-          if (codec == S3S_CODEC_SNAPPY) {
-            snappy_plan_chunk(h_items, it, ch, seg_offsets[g] + pos, len, p);
-            continue;
-          }
-          if (codec == S3S_CODEC_ZSTD) {
-            h_items[it++] = Item{seg_offsets[g] + pos, len, kItemZstdBlock | ((pos + len == u) << 8), ch++, p};
-            continue;
-          }
-          if (codec == S3S_CODEC_LZF) {
-            h_items[it++] = Item{seg_offsets[g] + pos, len, kItemLzfChunk, ch++, p};
-            continue;
-          }
-          h_items[it++] = Item{seg_offsets[g] + pos, len, lz4_chunk_kind(len) | (level << 8), ch++, p};
+          plan_codec_block(h_items, it, ch, codec, level, seg_offsets[g] + pos, len, p, pos + len == u);
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
       }
@@ -538,7 +526,7 @@ static int compress_core(s3s_ctx* ctx, int codec, int checksum_algo, const uint8
     if ((rc = ensure(ctx, B_PART_FIRST, pf_bytes))) return rc;
     // a slot holds one chunk's codec output: LZ4 payloads never exceed the chunk (RAW fallback), a raw
     // snappy block can grow to MaxCompressedLength(chunk); a Snappy slot holds at most one 64 KiB fragment
-    const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
+    const int64_t slot_stride = compress_slot_stride(codec, bs);
     if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(n_chunks > 0 ? n_chunks : 1)))) return rc;
     if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
     if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * (size_t)(n_items + 1)))) return rc;
@@ -811,19 +799,7 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
         if (codec == S3S_CODEC_ZSTD) h_items[it++] = Item{u, 0, kItemZstdHeader, -1, p};
         for (int64_t pos = 0; pos < u; pos += bs) {
           const int32_t len = (int32_t)((u - pos) < bs ? (u - pos) : bs);
-          if (codec == S3S_CODEC_SNAPPY) {
-            snappy_plan_chunk(h_items, it, ch, delta + k.src_offsets[p] + pos, len, p);
-            continue;
-          }
-          if (codec == S3S_CODEC_ZSTD) {
-            h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kItemZstdBlock | ((pos + len == u) << 8), ch++, p};
-            continue;
-          }
-          if (codec == S3S_CODEC_LZF) {
-            h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, kItemLzfChunk, ch++, p};
-            continue;
-          }
-          h_items[it++] = Item{delta + k.src_offsets[p] + pos, len, lz4_chunk_kind(len) | (level << 8), ch++, p};
+          plan_codec_block(h_items, it, ch, codec, level, delta + k.src_offsets[p] + pos, len, p, pos + len == u);
         }
         if (codec == S3S_CODEC_LZ4) h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, p};
       }
@@ -837,7 +813,7 @@ int s3s_compress_map_outputs_batch_device(s3s_ctx* ctx, int codec, int checksum_
     first_seg[(size_t)n_tasks] = seg;
   }
   const int32_t total_segs = first_seg[(size_t)n_tasks];
-  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
+  const int64_t slot_stride = compress_slot_stride(codec, bs);
   if ((rc = ensure(ctx, B_PLAN, L.total))) return rc;
   if ((rc = ensure(ctx, B_PARTIAL, 16 * (size_t)(total_segs > 0 ? total_segs : 1)))) return rc;
   if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(n_chunks > 0 ? n_chunks : 1)))) return rc;

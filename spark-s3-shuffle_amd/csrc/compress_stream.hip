@@ -6,10 +6,14 @@
 // Snappy chunks and LZF chunks are independent blocks cut at multiples of the block size from the partition's start, so a
 // stream that takes only whole blocks needs no device memory between feeds and writes the bytes of the one-shot call.
 //
-// A feed plans the units of its window on the host (compress_stream_core.h), launches the unchanged codec kernels into slots,
-// scans the item sizes (launch_scan_items), cuts the plan at the caller's capacity on the device (cstream_cut_kernel), gathers
-// the items in front of the cut (gather_items_cut_kernel, compress_stream_kernels.hip, reads the cut from device memory) and runs the checksums over the
-// pieces of partitions in the output, seeded with the open partition's carried state.  ONE host wait per feed, at its end.
+// Both feeds are the same phases: checks, plan, device work, take.  The rules of the first, second and last are HIP-free
+// functions of compress_stream_batch_core.h (over compress_stream_core.h) that the sanitized model programs call too; this file
+// holds what needs the context: the codec's functors (CsCodec), the buffers, the copies, the launches and the error texts.
+//
+// A feed plans its window as a batch of ONE on the host, launches the unchanged codec kernels into slots, scans the item sizes
+// (launch_scan_items), cuts the plan at the caller's capacity on the device (cstream_cut_kernel), gathers the items in front of
+// the cut (gather_items_cut_kernel, compress_stream_kernels.hip, reads the cut from device memory) and runs the checksums over
+// the pieces of partitions in the output, seeded with the open partition's carried state.  ONE host wait per feed, at its end.
 // (A workspace buffer that has to grow waits once more, as everywhere: ensure().)
 //
 // Under IO encryption (s3s_cstream_open_encrypted) a kItemIv record goes in front of the items of every unit that
@@ -45,16 +49,132 @@ struct s3s_cstream {
 
 namespace {
 
+using Entry = s3s_cstream_feed_entry;  // a window with its answer; the single feed makes one of its arguments
+
 inline int64_t fresh(int algo) { return algo == S3S_CHECKSUM_ADLER32 ? 1 : 0;  }  // getValue() of a new Adler32 / CRC32 / CRC32C
 
 inline int64_t need_src_unit(const s3s_cstream* s) { return s->codec == S3S_CODEC_NONE ? 1 : s->bs; }
 
 inline size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
 
-// the feed that wrote nothing: every end it passes closes a partition with what the stream already holds
-void finish_on_host(s3s_cstream* s, const s3s_cs::Cut& c, const int64_t* ends, int64_t* out_lengths, int64_t* out_checksums) {
-  s3s_cs::commit_nothing(&s->st, &s->carry, fresh(s->algo), c.parts_closed, out_lengths, out_checksums);
-  if (s->enc) s3s_cs::commit_nothing_iv(s->iv, c.parts_closed);
+inline bool with_sums(const s3s_cstream* s) { return s->algo != S3S_CHECKSUM_NONE; }
+
+inline uint8_t* carried_iv(s3s_cstream* s) { return s->enc ? s->iv : nullptr; }
+
+// ---- the error texts that more than one path answers with ------------------------------------------------------------------------
+int fail_need_dst(s3s_ctx* ctx, const Entry& e) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
+  return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld image bytes of the next unit", (long long)e.dst_capacity, (long long)e.result.need_dst);
+}
+int fail_iv_count(s3s_ctx* ctx, int64_t want) {
+  return fail(ctx, S3S_E_INVALID, "the entries of the batch have %lld pieces (n_ends + 1 each), s3s_set_stream_ivs gave %lld IVs", (long long)want,
+              (long long)ctx->iv_cur_n);
+}
+int fail_entries(s3s_ctx* ctx) { return fail(ctx, S3S_E_INVALID, "null entry array or negative count"); }
+
+inline bool null_with_length(const Entry& e) {
+  return (e.src_len > 0 && !e.d_src) || (e.dst_capacity > 0 && !e.d_dst) ||
+         (e.n_ends > 0 && (!e.part_ends || !e.out_lengths || (with_sums(e.stream) && !e.out_checksums)));
+}
+inline bool refused(const Entry& e) { return s3s_cs::window_refused(e.src_len, e.part_ends, e.n_ends, e.dst_capacity, null_with_length(e)); }
+
+// ---- what the codec of a stream makes of a unit (s3s_ctx.h): the functors of the HIP-free core, and the codec launch -------------
+struct CsCodec {
+  const s3s_cstream* s0;  // the stream, or the first of a batch: its codec, block size and variants are the call's
+  int codec;
+  int64_t bs;
+  bool enc;
+  int level;
+  CsCodec(const s3s_cstream* s, bool encrypted)
+      : s0(s), codec(s->codec), bs(s->bs), enc(encrypted), level(s->codec == S3S_CODEC_LZ4 ? lz4_level(s->bs) : 0) {}
+
+  int64_t items_of(const s3s_cs::Unit& u) const { return codec == S3S_CODEC_SNAPPY ? u.first + snappy_chunk_items(u.len) : 1; }
+  int64_t slots_of(const s3s_cs::Unit& u) const { return codec == S3S_CODEC_SNAPPY ? snappy_chunk_slots(u.len) : u.len > 0; }
+  s3s_cs::Count count(const Entry& e) const {
+    return s3s_cs::count_window(codec, bs, e.stream->st.open_bytes, e.src_len, e.part_ends, e.n_ends, enc,
+                                [&](const s3s_cs::Unit& u) { return items_of(u); }, [&](const s3s_cs::Unit& u) { return slots_of(u); });
+  }
+  // checksum segments of every piece, from an upper bound of its image bytes (a stream header and an end frame on top of what
+  // the one-shot call allows a partition of the piece's source bytes, and its IV); < 0: "window too large for one feed"
+  int64_t segs(const Entry& e, int32_t* seg_start) const {
+    return s3s_cs::piece_segs(e.src_len, e.part_ends, e.n_ends, seg_start, [&](int64_t bytes) {
+      return worst_segs(max_partition_size(codec, bs, bytes) + kLz4FrameHeader + kSnappyStreamHeader + (enc ? 16 : 0));
+    });
+  }
+  // The plan records of a window at its places in the call's arrays, sources seen from the call's base pointer (delta).
+  // false: they do not match the count the window was reserved with
+  bool plan(s3s_cs::CutEntry* c, const Entry& e, int64_t delta, Item* items, s3s_cs::Mark* marks, int32_t* part_first) const {
+    return s3s_cs::plan_entry_records(
+        c, codec, bs, e.stream->st.open_bytes, e.src_len, e.part_ends, e.n_ends, marks, part_first, enc, [&](const s3s_cs::Unit& u) { return items_of(u); },
+        [&](const s3s_cs::Unit& u, int32_t at) { items[at] = Item{0, 0, kItemIv, -1, u.piece}; },  // the hole the encrypt pass fills
+        [&](const s3s_cs::Unit& u, int32_t at, int32_t& slot) {
+          if (codec == S3S_CODEC_SNAPPY && u.first) items[at++] = Item{0, 0, kItemSnappyHeader, -1, u.piece};
+          if (u.len > 0) plan_codec_block(items, at, slot, codec, level, delta + u.src_off, u.len, u.piece, false);
+          else if (codec == S3S_CODEC_LZ4) items[at] = Item{0, 0, kItemLz4End | (level << 8), -1, u.piece};  // (plan_units: LZ4 alone has a unit without bytes)
+        });
+  }
+  int64_t slot_stride() const { return compress_slot_stride(codec, bs); }
+  int launch(s3s_ctx* ctx, const uint8_t* base, const Item* d_items, int32_t n_items) const {
+    if (codec == S3S_CODEC_LZ4) {
+      ctx->lz4_variant_used = s0->lz4_variant;
+      launch_lz4_compress(base, d_items, n_items, dev<uint32_t>(ctx, B_ITEM_CHECK), dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride(),
+                          dev<uint32_t>(ctx, B_ITEM_SIZE), dev<uint32_t>(ctx, B_WORK), (s0->lz4_variant == 11 ? 8 : 10) * ctx->cu_count,
+                          s0->lz4_variant, ctx->stream, nullptr, bs >= kLz4U32From);
+    } else if (codec == S3S_CODEC_LZF) {
+      launch_lzf_compress(base, d_items, n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride(), dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);
+    } else {
+      launch_snappy_compress(base, d_items, n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride(), dev<uint32_t>(ctx, B_ITEM_SIZE), s0->snappy_variant,
+                             ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return S3S_OK;
+  }
+};
+
+// the arrays of a call's s3s_cs::Arena in the pinned staging area
+struct CsStage {
+  uint8_t* hs;
+  Item* items;
+  s3s_cs::Mark* marks;
+  int32_t *pf, *seg, *pw, *status;
+  int64_t *seed, *res, *piece, *len, *sums;
+  uint8_t* ivs;
+  template <typename T>
+  T* at(size_t off) const { return reinterpret_cast<T*>(hs + off); }
+  CsStage(s3s_ctx* ctx, const s3s_cs::Arena& A)
+      : hs(static_cast<uint8_t*>(ctx->h_stage)), items(at<Item>(A.items)), marks(at<s3s_cs::Mark>(A.marks)), pf(at<int32_t>(A.pf)),
+        seg(at<int32_t>(A.seg)), pw(at<int32_t>(A.pw)), status(at<int32_t>(A.status)), seed(at<int64_t>(A.seed)), res(at<int64_t>(A.res)),
+        piece(at<int64_t>(A.piece)), len(at<int64_t>(A.len)), sums(at<int64_t>(A.sums)), ivs(hs + A.ivs) {}
+};
+
+s3s_cs::Arena lay_out(const s3s_cs::Totals& tot, bool enc, int64_t tiles) {
+  s3s_cs::Arena A;
+  if (enc) A.lay_out_encrypted(tot, sizeof(Item), sizeof(TaskTail), sizeof(s3s_cs::PassWindow), tiles);
+  else A.lay_out(tot, sizeof(Item), sizeof(TaskTail));
+  return A;
+}
+
+// Window wi of a call into the staging arrays: plan records, seeds, and under IO encryption its
+// IVs (slice: the window's own of the call's; entry 0 is the stream's while the open partition already has image bytes)
+bool stage_window(const CsCodec& k, const CsStage& h, s3s_cs::CutEntry* c, int32_t wi, const Entry& e, int64_t delta,
+                  const uint8_t* slice) {
+  const s3s_cstream* s = e.stream;
+  if (!k.plan(c, e, delta, h.items, h.marks, h.pf)) return false;
+  s3s_cs::seed_pieces(*c, wi, s->carry, fresh(s->algo), h.seed, h.pw);
+  if (k.enc) s3s_cs::window_ivs(*c, slice, 0, s->iv, h.ivs);
+  return true;
+}
+
+// behind the download: the words of a window's cut, checked
+bool words_ok(const CsStage& h, int32_t wi, const s3s_cs::CutEntry& c, const Entry& e, s3s_cs::Cut* cut) {
+  return s3s_cs::cut_from_words(h.res + (size_t)s3s_cs::kCutWords * (size_t)wi, h.status[wi], c.n_items, e.src_len, e.dst_capacity, e.n_ends, cut);
+}
+// ... and taken: the stream moves, the entry has its answer
+int take(s3s_ctx* ctx, const CsStage& h, const s3s_cs::CutEntry& c, const s3s_cs::Cut& cut, Entry& e) {
+  s3s_cstream* s = e.stream;
+  if (!s3s_cs::take_window(&s->st, &s->carry, carried_iv(s), cut, e.part_ends, h.piece + c.first_pp, h.len + c.first_len,
+                           with_sums(s) ? h.sums + c.first_piece : nullptr, h.ivs + 16 * (size_t)c.first_piece, e.out_lengths, e.out_checksums, &e.result))
+    return fail_need_dst(ctx, e);
+  return S3S_OK;
 }
 
 int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, bool encrypted, s3s_cstream** out) {
@@ -89,6 +209,194 @@ int open_stream(s3s_ctx* ctx, int codec, int checksum_algo, bool encrypted, s3s_
   s->epoch = ctx->enc_epoch;
   *out = s;
   return S3S_OK;
+}
+
+// ---- the single feed, phase by phase ----------------------------------------------------------------------------------------
+// checks: the arguments, the key setting the stream is bound to, one IV per piece - before anything is launched
+int feed_checks(const Entry& e) {
+  const s3s_cstream* s = e.stream;
+  s3s_ctx* ctx = s->ctx;
+  if (refused(e))
+    return fail(ctx, S3S_E_INVALID, "%s",
+                e.src_len < 0 || e.n_ends < 0 || e.dst_capacity < 0 ? "negative size"
+                : null_with_length(e)                                ? "null pointer with a non-zero length"
+                                                                     : "part_ends must be ascending offsets inside the window");
+  if (s->enc && (s->epoch != ctx->enc_epoch || !enc_on(ctx)))  // bound to the key setting it was opened under: it can only be closed
+    return fail(ctx, S3S_E_INVALID, "s3s_set_io_encryption was called after the stream was opened: the stream can only be closed");
+  if (!s->enc && enc_on(ctx)) return fail(ctx, S3S_E_UNSUPPORTED, "IO encryption was switched on after the stream was opened");
+  return s->enc ? enc_check_ivs(ctx, e.n_ends + 1) : S3S_OK;  // the partitions that end in the window, and the one it leaves open
+}
+
+// device work, first step: the buffers of every feed, the status and result words zeroed, the feed's IVs (staged at h_ivs) up
+int feed_begin(const Entry& e, const uint8_t* h_ivs) {
+  s3s_ctx* ctx = e.stream->ctx;
+  const size_t n_pieces = (size_t)e.n_ends + 1;
+  int rc;
+  if ((rc = ensure(ctx, B_INDEX, 8 * (n_pieces + 1)))) return rc;
+  if ((rc = ensure(ctx, B_SUMS, 8 * (n_pieces + 1)))) return rc;
+  if ((rc = ensure(ctx, B_REF_SUMS, 8 * (n_pieces + 1)))) return rc;
+  if ((rc = ensure(ctx, B_STATUS, 128))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, 128, ctx->stream));
+  if (e.stream->enc) {
+    if ((rc = ensure(ctx, B_IVS, 16 * n_pieces))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_IVS].p, h_ivs, 16 * n_pieces, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return S3S_OK;
+}
+
+// device work, last step: the checksums over the pieces as the cut left them (offsets in B_INDEX), the open partition's state
+// as the first piece's seed; the status word; the feed's ONE wait
+int feed_sums_and_wait(const Entry& e, const int32_t* h_seg, const int64_t* h_seed, int64_t* h_sums, int32_t* h_status) {
+  const s3s_cstream* s = e.stream;
+  s3s_ctx* ctx = s->ctx;
+  const int32_t n_pieces = e.n_ends + 1;
+  int64_t* d_piece = dev<int64_t>(ctx, B_INDEX);
+  int rc;
+  if (with_sums(s)) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_REF_SUMS].p, h_seed, 8 * (size_t)n_pieces, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_checksum(ctx, s->algo, e.d_dst, d_piece, n_pieces, h_seg, dev<int64_t>(ctx, B_SUMS), e.dst_capacity))) return rc;
+    launch_checksum_seed(s->algo, d_piece, n_pieces, ctx->buf[B_TABLES].p, dev<int64_t>(ctx, B_REF_SUMS), dev<int64_t>(ctx, B_SUMS), ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_sums, ctx->buf[B_SUMS].p, 8 * (size_t)n_pieces, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(h_status, ctx->buf[B_STATUS].p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return S3S_OK;
+}
+
+// spark.shuffle.compress=false: the partition bytes are the image, the cut is known on the host.  Under IO encryption:
+// IV | window bytes XOR key stream, in one pass from the source
+int feed_none(Entry& e) {
+  s3s_cstream* s = e.stream;
+  s3s_ctx* ctx = s->ctx;
+  const bool enc = s->enc;
+  const int32_t n_ends = e.n_ends, n_pieces = n_ends + 1;
+  const int64_t front = s->st.open_img;  // stored bytes of the open partition that earlier feeds wrote
+  const s3s_cs::Cut c = enc ? s3s_cs::none_cut_encrypted(front, e.src_len, e.part_ends, n_ends, e.dst_capacity, nullptr)
+                            : s3s_cs::none_cut(e.src_len, e.part_ends, n_ends, e.dst_capacity);
+  if (c.need_dst) {
+    e.result.need_dst = c.need_dst;
+    return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld", (long long)e.dst_capacity, (long long)c.need_dst);
+  }
+  if (c.out_len == 0) {  // nothing to write: no device work
+    s3s_cs::answer_on_host(&s->st, &s->carry, carried_iv(s), fresh(s->algo), c, e.out_lengths, e.out_checksums, &e.result);
+    return S3S_OK;
+  }
+  // pinned staging: [seg_start n_pieces + 1][piece offsets n_pieces + 1][seeds n_pieces] | down: [sums n_pieces][status]
+  //                 encrypted, up: [IVs n_pieces][plain piece offsets n_pieces + 1]
+  const size_t np1 = (size_t)n_pieces + 1;
+  const size_t o_up = al16(4 * np1), o_seed = al16(o_up + 8 * np1), o_sums = al16(o_seed + 8 * np1), o_status = al16(o_sums + 8 * np1),
+               o_ivs = o_status + 16, o_plain = al16(o_ivs + 16 * (size_t)n_pieces);
+  int rc;
+  if ((rc = ensure_stage(ctx, enc ? o_plain + 8 * np1 : o_ivs))) return rc;
+  uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
+  int32_t* h_seg = reinterpret_cast<int32_t*>(hs);
+  int64_t* h_up = reinterpret_cast<int64_t*>(hs + o_up);
+  int64_t* h_seed = reinterpret_cast<int64_t*>(hs + o_seed);
+  int64_t* h_plain = reinterpret_cast<int64_t*>(hs + o_plain);
+  uint8_t* h_ivs = hs + o_ivs;
+  s3s_cs::CutEntry pieces = {};  // (the pieces of a plan of one window without items)
+  pieces.n_pieces = n_pieces;
+  pieces.open_img = front;
+  if (CsCodec(s, enc).segs(e, h_seg) < 0) return fail(ctx, S3S_E_UNSUPPORTED, "window too large for one feed");
+  s3s_cs::seed_pieces(pieces, 0, s->carry, fresh(s->algo), h_seed, nullptr);
+  if (enc) s3s_cs::window_ivs(pieces, ctx->iv_cur, 0, s->iv, h_ivs);
+  if ((rc = feed_begin(e, h_ivs))) return rc;
+  int64_t* d_piece = dev<int64_t>(ctx, B_INDEX);
+  if (enc) {
+    s3s_cs::none_cut_encrypted(front, e.src_len, e.part_ends, n_ends, e.dst_capacity, h_up);
+    h_plain[0] = 0;
+    for (int32_t j = 0; j < n_ends; j++) h_plain[j + 1] = e.part_ends[j];
+    h_plain[n_pieces] = e.src_len;
+    if ((rc = ensure(ctx, B_CRYPT_OFF, 8 * np1))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_piece, h_up, 8 * np1, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_CRYPT_OFF].p, h_plain, 8 * np1, hipMemcpyHostToDevice, ctx->stream));
+    launch_aes_ctr_cstream(kCsFromPlain, ctx->enc_keys, ctx->enc_rounds, e.d_src, e.d_dst, d_piece, dev<int64_t>(ctx, B_CRYPT_OFF),
+                           dev<uint8_t>(ctx, B_IVS), nullptr, n_pieces, front, c.out_len, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+  } else {
+    h_up[0] = 0;
+    for (int32_t j = 0; j < n_ends; j++) h_up[j + 1] = e.part_ends[j] < c.out_len ? e.part_ends[j] : c.out_len;
+    h_up[n_pieces] = c.out_len;
+    HIP_TRY(ctx, hipMemcpyAsync(e.d_dst, e.d_src, (size_t)c.out_len, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_piece, h_up, 8 * np1, hipMemcpyHostToDevice, ctx->stream));
+  }
+  int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);
+  if ((rc = feed_sums_and_wait(e, h_seg, h_seed, h_sums, reinterpret_cast<int32_t*>(hs + o_status)))) return rc;
+  s3s_cs::take_window(&s->st, &s->carry, carried_iv(s), c, e.part_ends, h_up, nullptr, with_sums(s) ? h_sums : nullptr, h_ivs, e.out_lengths,
+                      e.out_checksums, &e.result);  // (need_dst was answered in front of the device work)
+  return S3S_OK;
+}
+
+// A codec's window: the plan is a batch of ONE on the host (the records, places and staging layout of the batched feed with
+// every first_* = 0); the device work keeps the single kernels and its own copies into the context's buffers
+int feed_codec(Entry& e) {
+  s3s_cstream* s = e.stream;
+  s3s_ctx* ctx = s->ctx;
+  const bool enc = s->enc;
+  const CsCodec k(s, enc);
+  const int32_t n_pieces = e.n_ends + 1;
+  int rc;
+  // ---- plan ----------------------------------------------------------------------------------------------------------------
+  const s3s_cs::Count n = k.count(e);
+  if (n.items > s3s_cs::kBatchMax) return fail(ctx, S3S_E_UNSUPPORTED, "too many codec blocks in one window");
+  if (n.items == 0) {  // nothing to write: no device work
+    s3s_cs::answer_on_host(&s->st, &s->carry, carried_iv(s), fresh(s->algo), s3s_cs::cut_nothing(e.n_ends, need_src_unit(s)), e.out_lengths,
+                           e.out_checksums, &e.result);
+    return S3S_OK;
+  }
+  s3s_cs::Totals tot;  // (the segments are sized straight into the staging area, below: the single kernels do not read n_segs)
+  s3s_cs::CutEntry c = s3s_cs::reserve(&tot, n.items, n.slots, e.n_ends, 0, e.dst_capacity, s->st.open_img);
+  const s3s_cs::Arena A = lay_out(tot, enc, 0);
+  if ((rc = ensure_stage(ctx, A.total))) return rc;
+  const CsStage h(ctx, A);
+  if (k.segs(e, h.seg) < 0) return fail(ctx, S3S_E_UNSUPPORTED, "window too large for one feed");
+  if (!stage_window(k, h, &c, 0, e, 0, ctx->iv_cur)) return fail(ctx, S3S_E_HIP, "the window's plan does not match its count");
+
+  // ---- device work ---------------------------------------------------------------------------------------------------------
+  if ((rc = feed_begin(e, h.ivs))) return rc;
+  const size_t np1 = (size_t)n_pieces + 1, n_items = (size_t)c.n_items;
+  if ((rc = ensure(ctx, B_ITEMS, sizeof(Item) * n_items + 16))) return rc;
+  if ((rc = ensure(ctx, B_PLAN, sizeof(s3s_cs::Mark) * n_items + 16))) return rc;
+  if ((rc = ensure(ctx, B_PART_FIRST, 4 * np1))) return rc;
+  if ((rc = ensure(ctx, B_SLOTS, (size_t)k.slot_stride() * (size_t)(c.n_slots > 0 ? c.n_slots : 1)))) return rc;
+  if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (n_items + 1)))) return rc;
+  if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * (n_items + 1)))) return rc;
+  if ((rc = ensure(ctx, B_ITEM_CHECK, sizeof(uint32_t) * (n_items + 1)))) return rc;
+  if ((rc = ensure(ctx, B_WORK, 64))) return rc;
+  if ((rc = ensure(ctx, B_OFFSETS, 8 * np1))) return rc;
+  if ((rc = ensure(ctx, B_FRAME_OUT, 8 * np1))) return rc;
+  const Item* d_items = dev<Item>(ctx, B_ITEMS);
+  int64_t* d_piece = dev<int64_t>(ctx, B_INDEX);
+  int32_t* d_status = dev<int32_t>(ctx, B_STATUS);
+  int64_t* d_result = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_STATUS) + 16);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_ITEMS].p, h.items, sizeof(Item) * n_items, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_PLAN].p, h.marks, sizeof(s3s_cs::Mark) * n_items, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_PART_FIRST].p, h.pf, 4 * np1, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = k.launch(ctx, e.d_src, d_items, c.n_items))) return rc;
+  if (enc) launch_seed_iv_items(d_items, c.n_items, dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);
+  // (the scan's own index - the unclamped piece offsets - goes to a buffer nobody reads: the cut kernel writes the clamped ones)
+  launch_scan_items(d_items, dev<uint32_t>(ctx, B_ITEM_SIZE), c.n_items, dev<int64_t>(ctx, B_ITEM_OFF), dev<int32_t>(ctx, B_PART_FIRST), n_pieces,
+                    dev<int64_t>(ctx, B_OFFSETS), ctx->stream);
+  launch_cstream_cut(ctx->buf[B_PLAN].p, dev<int64_t>(ctx, B_ITEM_OFF), c.n_items, dev<int32_t>(ctx, B_PART_FIRST), n_pieces, e.dst_capacity,
+                     c.first_last, c.ends0, c.open_img, d_result, d_piece, dev<int64_t>(ctx, B_FRAME_OUT), ctx->stream);
+  launch_gather_items_cut(e.d_src, d_items, c.n_items, d_result, dev<uint8_t>(ctx, B_SLOTS), k.slot_stride(), dev<uint32_t>(ctx, B_ITEM_SIZE),
+                          dev<int64_t>(ctx, B_ITEM_OFF), e.d_dst, e.dst_capacity, d_status, ctx->stream);
+  if (enc) {  // IVs into the holes, key stream over the rest of d_dst[0, out_len): out_len is the cut kernel's, the grid a host bound
+    const int64_t bound = s3s_cs::feed_bound_encrypted(k.codec, k.bs, e.src_len, e.n_ends);
+    launch_aes_ctr_cstream(kCsInPlace, ctx->enc_keys, ctx->enc_rounds, nullptr, e.d_dst, d_piece, nullptr, dev<uint8_t>(ctx, B_IVS), d_result, n_pieces,
+                           c.open_img, bound < e.dst_capacity ? bound : e.dst_capacity, ctx->stream);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(h.res, d_result, 8 * s3s_cs::kCutWords, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(h.piece, d_piece, 8 * np1, hipMemcpyDeviceToHost, ctx->stream));
+  if (e.n_ends > 0) HIP_TRY(ctx, hipMemcpyAsync(h.len, ctx->buf[B_FRAME_OUT].p, 8 * (size_t)e.n_ends, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = feed_sums_and_wait(e, h.seg, h.seed, h.sums, h.status))) return rc;
+
+  // ---- take: the words checked, then the stream moves -----------------------------------------------------------------------
+  s3s_cs::Cut cut;
+  if (!words_ok(h, 0, c, e, &cut)) return fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible result");
+  return take(ctx, h, c, cut, e);
 }
 
 }  // namespace
@@ -127,240 +435,13 @@ int s3s_cstream_feed_device(s3s_cstream* s, const uint8_t* d_src, int64_t src_le
   memset(r, 0, sizeof *r);
   std::optional<IvScope> iv_scope;  // an encrypted stream's feed is a compress call: it consumes the IVs of s3s_set_stream_ivs either way
   if (s->enc) iv_scope.emplace(ctx);
-  const bool enc = s->enc;
-  const int codec = s->codec;
-  const bool do_sum = s->algo != S3S_CHECKSUM_NONE;
-  if (src_len < 0 || n_ends < 0 || dst_capacity < 0) return fail(ctx, S3S_E_INVALID, "negative size");
-  if ((src_len > 0 && !d_src) || (dst_capacity > 0 && !d_dst) || (n_ends > 0 && (!part_ends || !out_lengths || (do_sum && !out_checksums))))
-    return fail(ctx, S3S_E_INVALID, "null pointer with a non-zero length");
-  if (!s3s_cs::ends_valid(src_len, part_ends, n_ends))
-    return fail(ctx, S3S_E_INVALID, "part_ends must be ascending offsets inside the window");
-  if (enc && (s->epoch != ctx->enc_epoch || !enc_on(ctx)))  // bound to the key setting it was opened under: it can only be closed
-    return fail(ctx, S3S_E_INVALID, "s3s_set_io_encryption was called after the stream was opened: the stream can only be closed");
-  if (!enc && enc_on(ctx)) return fail(ctx, S3S_E_UNSUPPORTED, "IO encryption was switched on after the stream was opened");
-  const int32_t n_pieces = n_ends + 1;  // the partitions that end in the window, and the one it leaves open
-  if (enc)  // one IV per piece, before anything is launched
-    if (int iv_rc = enc_check_ivs(ctx, n_pieces)) return iv_rc;
+  Entry e = {s, d_src, src_len, part_ends, n_ends, S3S_OK, d_dst, dst_capacity, out_lengths, out_checksums, {}};
+  if (int rc = feed_checks(e)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!do_sum) out_checksums = nullptr;
-  const int64_t bs = s->bs;
-  const int64_t front = s->st.open_img;  // stored bytes of the open partition that earlier feeds wrote
-  int rc;
-
-  // ---- plan: count, then build ----------------------------------------------------------------------------------------------
-  s3s_cs::Cut c;
-  int64_t n_items64 = 0, n_slots64 = 0;
-  s3s_cs::Plan plan;
-  if (codec == S3S_CODEC_NONE) {
-    c = enc ? s3s_cs::none_cut_encrypted(front, src_len, part_ends, n_ends, dst_capacity, nullptr)
-            : s3s_cs::none_cut(src_len, part_ends, n_ends, dst_capacity);
-    if (c.need_dst) {
-      r->need_dst = c.need_dst;
-      return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld", (long long)dst_capacity, (long long)c.need_dst);
-    }
-  } else {
-    plan = s3s_cs::plan_units(codec, bs, s->st.open_bytes, src_len, part_ends, n_ends, [&](const s3s_cs::Unit& u) {
-      if (codec == S3S_CODEC_SNAPPY) {
-        n_items64 += s3s_cs::iv_records(u, enc) + u.first + snappy_chunk_items(u.len);
-        n_slots64 += snappy_chunk_slots(u.len);
-      } else {
-        n_items64 += s3s_cs::iv_records(u, enc) + 1;
-        n_slots64 += u.len > 0;
-      }
-    });
-    if (n_items64 > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "too many codec blocks in one window");
-    if (plan.n_units == 0) {
-      c.parts_closed = n_ends;
-      if (n_ends == 0) c.need_src = need_src_unit(s);
-    }
-  }
-  const int32_t n_items = (int32_t)n_items64, n_slots = (int32_t)n_slots64;
-  if (codec == S3S_CODEC_NONE ? c.out_len == 0 : n_items == 0) {  // nothing to write: no device work
-    finish_on_host(s, c, part_ends, out_lengths, out_checksums);
-    r->need_src = c.need_src;
-    r->parts_closed = c.parts_closed;
-    return S3S_OK;
-  }
-
-  // pinned staging: [items][marks][part_first n_pieces + 1][seg_start n_pieces + 1][piece offsets n_pieces + 1 (NONE: up)]
-  //                 [seeds n_pieces] | down: [result][piece offsets n_pieces + 1][lengths n_ends][sums n_pieces][status]
-  //                 encrypted, up: [IVs n_pieces][plain piece offsets n_pieces + 1 (NONE)]
-  const size_t np1 = (size_t)n_pieces + 1;
-  const size_t o_marks = al16(sizeof(Item) * (size_t)n_items), o_pf = al16(o_marks + sizeof(s3s_cs::Mark) * (size_t)n_items),
-               o_seg = al16(o_pf + 4 * np1), o_up = al16(o_seg + 4 * np1), o_seed = al16(o_up + 8 * np1),
-               o_res = al16(o_seed + 8 * np1), o_piece = al16(o_res + 8 * s3s_cs::kCutWords), o_len = al16(o_piece + 8 * np1),
-               o_sums = al16(o_len + 8 * np1), o_status = al16(o_sums + 8 * np1), o_ivs = o_status + 16,
-               o_plain = al16(o_ivs + 16 * (size_t)n_pieces), stage_total = enc ? o_plain + 8 * np1 : o_status + 16;
-  if ((rc = ensure_stage(ctx, stage_total))) return rc;
-  uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
-  Item* h_items = reinterpret_cast<Item*>(hs);
-  s3s_cs::Mark* h_marks = reinterpret_cast<s3s_cs::Mark*>(hs + o_marks);
-  int32_t* h_pf = reinterpret_cast<int32_t*>(hs + o_pf);
-  int32_t* h_seg = reinterpret_cast<int32_t*>(hs + o_seg);
-  int64_t* h_up = reinterpret_cast<int64_t*>(hs + o_up);
-  int64_t* h_seed = reinterpret_cast<int64_t*>(hs + o_seed);
-  int64_t* h_res = reinterpret_cast<int64_t*>(hs + o_res);
-  int64_t* h_piece = reinterpret_cast<int64_t*>(hs + o_piece);
-  int64_t* h_len = reinterpret_cast<int64_t*>(hs + o_len);
-  int64_t* h_sums = reinterpret_cast<int64_t*>(hs + o_sums);
-  int32_t* h_status = reinterpret_cast<int32_t*>(hs + o_status);
-  uint8_t* h_ivs = hs + o_ivs;
-
-  // checksum segments of every piece, from an upper bound of its image bytes (a stream header and an end frame on top of
-  // what the one-shot call allows a partition of the piece's source bytes)
-  int64_t segs = 0;
-  for (int32_t j = 0; j < n_pieces; j++) {
-    const int64_t a = j == 0 ? 0 : part_ends[j - 1], b = j < n_ends ? part_ends[j] : src_len;
-    h_seg[j] = (int32_t)segs;
-    segs += worst_segs(max_partition_size(codec, bs, b - a) + kLz4FrameHeader + kSnappyStreamHeader + (enc ? 16 : 0));
-    h_seed[j] = j == 0 ? s->carry : fresh(s->algo);
-    if (segs > 0x7fffff00ll) return fail(ctx, S3S_E_UNSUPPORTED, "window too large for one feed");
-  }
-  h_seg[n_pieces] = (int32_t)segs;
-
-  if ((rc = ensure(ctx, B_INDEX, 8 * np1))) return rc;
-  if ((rc = ensure(ctx, B_SUMS, 8 * np1))) return rc;
-  if ((rc = ensure(ctx, B_REF_SUMS, 8 * np1))) return rc;
-  if ((rc = ensure(ctx, B_STATUS, 128))) return rc;
-  int64_t* d_piece = dev<int64_t>(ctx, B_INDEX);
-  int32_t* d_status = dev<int32_t>(ctx, B_STATUS);
-  int64_t* d_result = reinterpret_cast<int64_t*>(dev<uint8_t>(ctx, B_STATUS) + 16);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->buf[B_STATUS].p, 0, 128, ctx->stream));
-  if (enc) {  // the feed's IVs, one upload; entry 0 is the stream's own while the open partition already has image bytes
-    if ((rc = ensure(ctx, B_IVS, 16 * (size_t)n_pieces))) return rc;
-    memcpy(h_ivs, ctx->iv_cur, 16 * (size_t)n_pieces);
-    if (front > 0) memcpy(h_ivs, s->iv, 16);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_IVS].p, h_ivs, 16 * (size_t)n_pieces, hipMemcpyHostToDevice, ctx->stream));
-  }
-
-  if (codec == S3S_CODEC_NONE && enc) {
-    // spark.shuffle.compress=false under IO encryption: IV | window bytes XOR key stream, in one pass from the source
-    int64_t* h_plain = reinterpret_cast<int64_t*>(hs + o_plain);
-    s3s_cs::none_cut_encrypted(front, src_len, part_ends, n_ends, dst_capacity, h_up);
-    h_plain[0] = 0;
-    for (int32_t j = 0; j < n_ends; j++) h_plain[j + 1] = part_ends[j];
-    h_plain[n_pieces] = src_len;
-    if ((rc = ensure(ctx, B_CRYPT_OFF, 8 * np1))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_piece, h_up, 8 * np1, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_CRYPT_OFF].p, h_plain, 8 * np1, hipMemcpyHostToDevice, ctx->stream));
-    launch_aes_ctr_cstream(kCsFromPlain, ctx->enc_keys, ctx->enc_rounds, d_src, d_dst, d_piece, dev<int64_t>(ctx, B_CRYPT_OFF),
-                           dev<uint8_t>(ctx, B_IVS), nullptr, n_pieces, front, c.out_len, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-  } else if (codec == S3S_CODEC_NONE) {
-    // spark.shuffle.compress=false: the partition bytes are the image; the cut is known on the host
-    h_up[0] = 0;
-    for (int32_t j = 0; j < n_ends; j++) h_up[j + 1] = part_ends[j] < c.out_len ? part_ends[j] : c.out_len;
-    h_up[n_pieces] = c.out_len;
-    HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, (size_t)c.out_len, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_piece, h_up, 8 * np1, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    // items, marks and the first item of every piece, in image order.  A unit's marks learn how many ends lie behind it when
-    // the next unit arrives (that one's ends_before); the last unit's is every end of the window
-    const int level = codec == S3S_CODEC_LZ4 ? lz4_level(bs) : 0;
-    int32_t it = 0, slot = 0, piece = 0, first_last = -1, ends0 = 0, prev0 = 0;
-    bool fits = true;  // the records stay inside what the count above sized
-    h_pf[0] = 0;
-    s3s_cs::plan_units(codec, bs, s->st.open_bytes, src_len, part_ends, n_ends, [&](const s3s_cs::Unit& u) {
-      const int64_t mine = s3s_cs::iv_records(u, enc) + (codec == S3S_CODEC_SNAPPY ? u.first + snappy_chunk_items(u.len) : 1);
-      if (!fits || it + mine > n_items) {
-        fits = false;
-        return;
-      }
-      s3s_cs::mark_ends_after(h_marks, prev0, it, u.ends_before);
-      if (it == 0) ends0 = u.ends_before;
-      while (piece < u.piece) h_pf[++piece] = it;
-      prev0 = it;
-      if (s3s_cs::iv_records(u, enc)) h_items[it++] = Item{0, 0, kItemIv, -1, u.piece};  // the hole the encrypt pass fills
-      if (codec == S3S_CODEC_SNAPPY) {
-        if (u.first) h_items[it++] = Item{0, 0, kItemSnappyHeader, -1, u.piece};
-        snappy_plan_chunk(h_items, it, slot, u.src_off, u.len, u.piece);
-      } else if (codec == S3S_CODEC_LZF) {
-        h_items[it++] = Item{u.src_off, u.len, kItemLzfChunk, slot++, u.piece};
-      } else if (u.len > 0) {
-        h_items[it++] = Item{u.src_off, u.len, lz4_chunk_kind(u.len) | (level << 8), slot++, u.piece};
-      } else {
-        h_items[it++] = Item{0, 0, kItemLz4End | (level << 8), -1, u.piece};
-      }
-      s3s_cs::mark_unit(h_marks, prev0, it, u, n_ends);
-      if (first_last < 0) first_last = it - 1;
-    });
-    while (piece < n_pieces) h_pf[++piece] = it;
-    if (!fits || it != n_items || slot != n_slots) return fail(ctx, S3S_E_HIP, "the window's plan does not match its count");
-
-    const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
-    if ((rc = ensure(ctx, B_ITEMS, sizeof(Item) * (size_t)n_items + 16))) return rc;
-    if ((rc = ensure(ctx, B_PLAN, sizeof(s3s_cs::Mark) * (size_t)n_items + 16))) return rc;
-    if ((rc = ensure(ctx, B_PART_FIRST, 4 * np1))) return rc;
-    if ((rc = ensure(ctx, B_SLOTS, (size_t)slot_stride * (size_t)(n_slots > 0 ? n_slots : 1)))) return rc;
-    if ((rc = ensure(ctx, B_ITEM_SIZE, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
-    if ((rc = ensure(ctx, B_ITEM_OFF, sizeof(int64_t) * (size_t)(n_items + 1)))) return rc;
-    if ((rc = ensure(ctx, B_ITEM_CHECK, sizeof(uint32_t) * (size_t)(n_items + 1)))) return rc;
-    if ((rc = ensure(ctx, B_WORK, 64))) return rc;
-    if ((rc = ensure(ctx, B_OFFSETS, 8 * np1))) return rc;
-    if ((rc = ensure(ctx, B_FRAME_OUT, 8 * np1))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_ITEMS].p, h_items, sizeof(Item) * (size_t)n_items, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_PLAN].p, h_marks, sizeof(s3s_cs::Mark) * (size_t)n_items, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_PART_FIRST].p, h_pf, 4 * np1, hipMemcpyHostToDevice, ctx->stream));
-    if (codec == S3S_CODEC_LZ4) {
-      ctx->lz4_variant_used = s->lz4_variant;
-      launch_lz4_compress(d_src, dev<Item>(ctx, B_ITEMS), n_items, dev<uint32_t>(ctx, B_ITEM_CHECK), dev<uint8_t>(ctx, B_SLOTS),
-                          (int32_t)slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<uint32_t>(ctx, B_WORK),
-                          (s->lz4_variant == 11 ? 8 : 10) * ctx->cu_count, s->lz4_variant, ctx->stream, nullptr, bs >= kLz4U32From);
-    } else if (codec == S3S_CODEC_LZF) {
-      launch_lzf_compress(d_src, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
-                          dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);
-    } else {
-      launch_snappy_compress(d_src, dev<Item>(ctx, B_ITEMS), n_items, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
-                             dev<uint32_t>(ctx, B_ITEM_SIZE), s->snappy_variant, ctx->stream);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    if (enc) launch_seed_iv_items(dev<Item>(ctx, B_ITEMS), n_items, dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);
-    // (the scan's own index - the unclamped piece offsets - goes to a buffer nobody reads: the cut kernel writes the clamped ones)
-    launch_scan_items(dev<Item>(ctx, B_ITEMS), dev<uint32_t>(ctx, B_ITEM_SIZE), n_items, dev<int64_t>(ctx, B_ITEM_OFF),
-                      dev<int32_t>(ctx, B_PART_FIRST), n_pieces, dev<int64_t>(ctx, B_OFFSETS), ctx->stream);
-    launch_cstream_cut(ctx->buf[B_PLAN].p, dev<int64_t>(ctx, B_ITEM_OFF), n_items, dev<int32_t>(ctx, B_PART_FIRST), n_pieces,
-                       dst_capacity, first_last, ends0, s->st.open_img, d_result, d_piece, dev<int64_t>(ctx, B_FRAME_OUT),
-                       ctx->stream);
-    launch_gather_items_cut(d_src, dev<Item>(ctx, B_ITEMS), n_items, d_result, dev<uint8_t>(ctx, B_SLOTS), slot_stride,
-                            dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF), d_dst, dst_capacity, d_status, ctx->stream);
-    if (enc) {  // IVs into the holes, key stream over the rest of d_dst[0, out_len): out_len is the cut kernel's, the grid a host bound
-      const int64_t bound = s3s_cs::feed_bound_encrypted(codec, bs, src_len, n_ends);
-      launch_aes_ctr_cstream(kCsInPlace, ctx->enc_keys, ctx->enc_rounds, nullptr, d_dst, d_piece, nullptr, dev<uint8_t>(ctx, B_IVS), d_result,
-                             n_pieces, front, bound < dst_capacity ? bound : dst_capacity, ctx->stream);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(h_res, d_result, 8 * s3s_cs::kCutWords, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h_piece, d_piece, 8 * np1, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_ends > 0) HIP_TRY(ctx, hipMemcpyAsync(h_len, ctx->buf[B_FRAME_OUT].p, 8 * (size_t)n_ends, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (do_sum) {  // over the pieces as the cut left them, the open partition's state as the first piece's seed
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[B_REF_SUMS].p, h_seed, 8 * (size_t)n_pieces, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_checksum(ctx, s->algo, d_dst, d_piece, n_pieces, h_seg, dev<int64_t>(ctx, B_SUMS), dst_capacity))) return rc;
-    launch_checksum_seed(s->algo, d_piece, n_pieces, ctx->buf[B_TABLES].p, dev<int64_t>(ctx, B_REF_SUMS), dev<int64_t>(ctx, B_SUMS), ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(h_sums, ctx->buf[B_SUMS].p, 8 * (size_t)n_pieces, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(h_status, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the feed's one wait
-
-  const int64_t* piece_off = h_up;
-  if (codec != S3S_CODEC_NONE) {
-    piece_off = h_piece;
-    if (!s3s_cs::cut_from_words(h_res, *h_status, n_items, src_len, dst_capacity, n_ends, &c))
-      return fail(ctx, S3S_E_HIP, "the capacity cut returned an impossible result");
-    if (c.need_dst > 0) {  // the first unit does not fit dst: nothing is taken, the stream stays usable
-      r->need_dst = c.need_dst;
-      return fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld image bytes of the next unit", (long long)dst_capacity, (long long)c.need_dst);
-    }
-  }
-  // (the commit step the batched feed shares: compress_stream_batch_core.h)
-  s3s_cs::commit(&s->st, &s->carry, c, part_ends, piece_off, codec != S3S_CODEC_NONE ? h_len : nullptr, do_sum ? h_sums : nullptr, out_lengths,
-                 out_checksums);
-  if (enc) s3s_cs::commit_iv(s->iv, s->st, front, c.parts_closed, h_ivs);  // (shared with the batched feed, like commit)
-  r->consumed = c.consumed;
-  r->out_len = c.out_len;
-  r->parts_closed = c.parts_closed;
-  return S3S_OK;
+  if (!with_sums(s)) e.out_checksums = nullptr;
+  const int rc = s->codec == S3S_CODEC_NONE ? feed_none(e) : feed_codec(e);
+  *r = e.result;
+  return rc;
 }
 
 int s3s_cstream_feed(s3s_cstream* s, const uint8_t* src, int64_t src_len, const int64_t* part_ends, int32_t n_ends, uint8_t* dst,
@@ -403,19 +484,22 @@ struct CsWin {
 
 struct CsBatch {
   s3s_ctx* ctx;
-  s3s_cstream_feed_entry* E;
+  Entry* E;
   int32_t n;
   std::vector<CsWin> W;
   std::vector<int32_t> host;  // entries the single feed answers without device work, in order
   bool enc = false;           // the batched path runs under IO encryption: every window is a keyed stream's
-  std::vector<int64_t> iv_at; // ... where every entry's slice of the call's IVs starts
   int64_t tiles = 0;          // ... the grid of the encrypt pass
-  const uint8_t* call_ivs = nullptr;  // ... the call's IVs (the IvScope's), before any entry's slice is set in iv_cur
+  // keyed streams on a keyed context: the call's IVs (the IvScope's) and where every entry's slice of them starts (n + 1)
+  const uint8_t* call_ivs = nullptr;
+  std::vector<int64_t> iv_at;
 
-  void single(s3s_cstream_feed_entry& e) {
-    if (enc) {  // the entry's slice of the call's IVs
-      ctx->iv_cur = call_ivs + 16 * (size_t)iv_at[(size_t)(&e - E)];
-      ctx->iv_cur_n = s3s_cs::iv_slice_len(e.n_ends);
+  const uint8_t* slice(int32_t i) const { return call_ivs + 16 * (size_t)iv_at[(size_t)i]; }
+  void single(int32_t i) {
+    Entry& e = E[i];
+    if (call_ivs) {  // the entry's slice of the call's IVs
+      ctx->iv_cur = slice(i);
+      ctx->iv_cur_n = iv_at[(size_t)i + 1] - iv_at[(size_t)i];
     }
     e.status = s3s_cstream_feed_device(e.stream, e.d_src, e.src_len, e.part_ends, e.n_ends, e.d_dst, e.dst_capacity, e.out_lengths,
                                        e.out_checksums, &e.result);
@@ -430,22 +514,6 @@ struct CsBatch {
     return S3S_OK;
   }
 };
-
-inline int64_t unit_items(int codec, const s3s_cs::Unit& u) { return codec == S3S_CODEC_SNAPPY ? u.first + snappy_chunk_items(u.len) : 1; }
-inline int64_t unit_slots(int codec, const s3s_cs::Unit& u) { return codec == S3S_CODEC_SNAPPY ? snappy_chunk_slots(u.len) : u.len > 0; }
-
-// worst-case checksum segments of a window's pieces, as the single feed sizes them; seg_start (or null): n_ends + 2 entries
-int64_t window_segs(int codec, int64_t bs, int64_t src_len, const int64_t* ends, int32_t n_ends, int32_t* seg_start, bool enc) {
-  int64_t segs = 0;
-  for (int32_t j = 0; j <= n_ends; j++) {
-    const int64_t a = j == 0 ? 0 : ends[j - 1], b = j < n_ends ? ends[j] : src_len;
-    if (seg_start) seg_start[j] = (int32_t)segs;
-    segs += worst_segs(max_partition_size(codec, bs, b - a) + kLz4FrameHeader + kSnappyStreamHeader + (enc ? 16 : 0));
-    if (segs > s3s_cs::kBatchMax) return -1;
-  }
-  if (seg_start) seg_start[n_ends + 1] = (int32_t)segs;
-  return segs;
-}
 
 // call-level refusals: nothing has been touched.  *batched: these streams go through the batched path - plain streams with
 // the layer off, or, with the layer on, the streams of s3s_cstream_open_encrypted under the context's current key setting
@@ -473,71 +541,27 @@ int cs_batch_check(CsBatch& b, bool* batched, bool* any_enc) {
   return S3S_OK;
 }
 
-// one by one, in order.  Encrypted streams: the call's IVs are sliced in entry order, n_ends + 1 an entry
-int cs_one_by_one(CsBatch& b, bool any_enc) {
-  s3s_ctx* ctx = b.ctx;
-  if (any_enc && enc_on(ctx)) {  // (with the layer off every encrypted stream is stale: the single feed's refusal)
-    int64_t want = 0;
-    for (int32_t i = 0; i < b.n; i++) want += (int64_t)(b.E[i].n_ends > 0 ? b.E[i].n_ends : 0) + 1;
-    if (ctx->iv_cur_n != want)
-      return fail(ctx, S3S_E_INVALID, "the entries of the batch have %lld pieces (n_ends + 1 each), s3s_set_stream_ivs gave %lld IVs",
-                  (long long)want, (long long)ctx->iv_cur_n);
-    const uint8_t* ivs = ctx->iv_cur;
-    for (int32_t i = 0; i < b.n; i++) {
-      const int64_t mine = (int64_t)(b.E[i].n_ends > 0 ? b.E[i].n_ends : 0) + 1;
-      ctx->iv_cur = ivs;
-      ctx->iv_cur_n = mine;
-      ivs += 16 * (size_t)mine;
-      b.single(b.E[i]);
-    }
-    return S3S_OK;
-  }
-  for (int32_t i = 0; i < b.n; i++) b.single(b.E[i]);
-  return S3S_OK;
-}
-
 // Which entries are windows of the batch: those whose single feed would launch something.  An entry the single feed refuses
-// by its arguments, and one whose window launches nothing, keep that feed's answer (b.host).  false: the call does not fit one
+// (by its arguments; under IO encryption a plain stream's S3S_E_UNSUPPORTED and a stale key setting's S3S_E_INVALID) and one
+// whose window launches nothing or is too large for a feed keep that feed's answer (b.host).  false: the call does not fit one
 // plan (an index would leave int32): it goes one by one
-bool cs_batch_windows(CsBatch& b, s3s_cs::Totals* tot) {
-  const s3s_cstream* s0 = b.E[0].stream;
-  const int codec = s0->codec;
-  const int64_t bs = s0->bs;
-  const bool do_sum = s0->algo != S3S_CHECKSUM_NONE;
-  const bool enc = b.enc;
-  s3s_cs::IvSlicer slices;
+bool cs_batch_windows(CsBatch& b, const CsCodec& k, s3s_cs::Totals* tot) {
   for (int32_t i = 0; i < b.n; i++) {
-    const s3s_cstream_feed_entry& e = b.E[i];
+    const Entry& e = b.E[i];
     const s3s_cstream* s = e.stream;
-    if (enc) b.iv_at.push_back(slices.take(e.n_ends));
-    if (enc && (!s->enc || s->epoch != b.ctx->enc_epoch)) {  // (the single feed's S3S_E_UNSUPPORTED / S3S_E_INVALID)
+    const bool no = (b.enc && (!s->enc || s->epoch != b.ctx->enc_epoch)) || refused(e);
+    const s3s_cs::Count n = no ? s3s_cs::Count() : k.count(e);
+    const int64_t segs = !no && n.items > 0 && with_sums(s) ? k.segs(e, nullptr) : 0;  // (sized only where checksums run)
+    if (s3s_cs::route_entry(no, n, segs) != s3s_cs::kRouteWindow) {
       b.host.push_back(i);
       continue;
     }
-    const bool null_with_length = (e.src_len > 0 && !e.d_src) || (e.dst_capacity > 0 && !e.d_dst) ||
-                                  (e.n_ends > 0 && (!e.part_ends || !e.out_lengths || (do_sum && !e.out_checksums)));
-    const bool refused = s3s_cs::window_refused(e.src_len, e.part_ends, e.n_ends, e.dst_capacity, null_with_length);
-    int64_t n_items = 0, n_slots = 0;
-    if (!refused)
-      s3s_cs::plan_units(codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, [&](const s3s_cs::Unit& u) {
-        n_items += s3s_cs::iv_records(u, enc) + unit_items(codec, u);
-        n_slots += unit_slots(codec, u);
-      });
-    if (refused || n_items == 0 || n_items > s3s_cs::kBatchMax) {  // (too many blocks: the single feed's S3S_E_UNSUPPORTED)
-      b.host.push_back(i);
-      continue;
-    }
-    const int64_t segs = do_sum ? window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, nullptr, enc) : 0;
-    if (segs < 0) {  // (window too large for one feed: the single feed's answer)
-      b.host.push_back(i);
-      continue;
-    }
-    if (!s3s_cs::fits_call(*tot, n_items, n_slots, e.n_ends, segs)) return false;
+    if (!s3s_cs::fits_call(*tot, n.items, n.slots, e.n_ends, segs)) return false;
     CsWin w;
     w.e = i;
-    w.c = s3s_cs::reserve(tot, n_items, n_slots, e.n_ends, segs, e.dst_capacity, s->st.open_img);
-    if (enc) {
-      w.tiles = s3s_cs::pass_tiles(e.dst_capacity, s3s_cs::feed_bound_encrypted(codec, bs, e.src_len, e.n_ends), s->st.open_img);
+    w.c = s3s_cs::reserve(tot, n.items, n.slots, e.n_ends, segs, e.dst_capacity, s->st.open_img);
+    if (b.enc) {
+      w.tiles = s3s_cs::pass_tiles(e.dst_capacity, s3s_cs::feed_bound_encrypted(k.codec, k.bs, e.src_len, e.n_ends), s->st.open_img);
       if (b.tiles + w.tiles > s3s_cs::kBatchMax) return false;
       b.tiles += w.tiles;
     }
@@ -546,19 +570,14 @@ bool cs_batch_windows(CsBatch& b, s3s_cs::Totals* tot) {
   return true;
 }
 
-int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
+int cs_batch_run(CsBatch& b, const CsCodec& k, const s3s_cs::Totals& tot) {
   s3s_ctx* ctx = b.ctx;
-  const s3s_cstream* s0 = b.E[0].stream;
-  const int codec = s0->codec, algo = s0->algo;
-  const int64_t bs = s0->bs;
-  const bool do_sum = algo != S3S_CHECKSUM_NONE;
+  const int algo = k.s0->algo;
+  const bool do_sum = with_sums(k.s0), enc = b.enc;
   const int32_t m = tot.m, N = (int32_t)tot.items;
   const size_t PP = (size_t)tot.pp(), P = (size_t)tot.pieces;
-  const bool enc = b.enc;
-  s3s_cs::Arena A;
-  if (enc) A.lay_out_encrypted(tot, sizeof(Item), sizeof(TaskTail), sizeof(s3s_cs::PassWindow), b.tiles);
-  else A.lay_out(tot, sizeof(Item), sizeof(TaskTail));
-  const int64_t slot_stride = codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
+  const s3s_cs::Arena A = lay_out(tot, enc, b.tiles);
+  const int64_t slot_stride = k.slot_stride();
   int rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if ((rc = ensure_stage(ctx, A.total))) return rc;
@@ -570,51 +589,25 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
   if ((rc = ensure(ctx, B_WORK, 64))) return rc;
   if ((rc = ensure(ctx, B_OFFSETS, 8 * PP))) return rc;
   if (do_sum && (rc = ensure(ctx, B_PARTIAL, 16 * (size_t)(tot.segs > 0 ? tot.segs : 1)))) return rc;
-  uint8_t* hs = static_cast<uint8_t*>(ctx->h_stage);
+  const CsStage h(ctx, A);
+  uint8_t* hs = h.hs;
   uint8_t* da = dev<uint8_t>(ctx, B_PLAN);
-  Item* h_items = reinterpret_cast<Item*>(hs + A.items);
-  s3s_cs::Mark* h_marks = reinterpret_cast<s3s_cs::Mark*>(hs + A.marks);
-  int32_t* h_pf = reinterpret_cast<int32_t*>(hs + A.pf);
-  int32_t* h_seg = reinterpret_cast<int32_t*>(hs + A.seg);
-  int64_t* h_seed = reinterpret_cast<int64_t*>(hs + A.seed);
-  int32_t* h_pw = reinterpret_cast<int32_t*>(hs + A.pw);
-  TaskTail* h_tails = reinterpret_cast<TaskTail*>(hs + A.tails);
-  s3s_cs::CutEntry* h_cuts = reinterpret_cast<s3s_cs::CutEntry*>(hs + A.cuts);
-  uint8_t* h_ivs = hs + A.ivs;  // under IO encryption: the IVs, the pass descriptors and the tile -> window map
-  s3s_cs::PassWindow* h_wins = reinterpret_cast<s3s_cs::PassWindow*>(hs + A.wins);
-  int32_t* h_tile_win = reinterpret_cast<int32_t*>(hs + A.tile_win);
+  TaskTail* h_tails = h.at<TaskTail>(A.tails);
+  s3s_cs::CutEntry* h_cuts = h.at<s3s_cs::CutEntry>(A.cuts);
+  s3s_cs::PassWindow* h_wins = h.at<s3s_cs::PassWindow>(A.wins);  // under IO encryption: the pass descriptors and the tile -> window map
+  int32_t* h_tile_win = h.at<int32_t>(A.tile_win);
   int32_t tile0 = 0;
 
   const uint8_t* base = b.E[b.W[0].e].d_src;  // the one source pointer of the codec launch: every item is an offset from it
-  const int level = codec == S3S_CODEC_LZ4 ? lz4_level(bs) : 0;
   memset(hs + A.seg, 0, A.seed - A.seg);
   for (int32_t wi = 0; wi < m; wi++) {
     CsWin& w = b.W[(size_t)wi];
-    const s3s_cstream_feed_entry& e = b.E[w.e];
-    const s3s_cstream* s = e.stream;
+    const Entry& e = b.E[w.e];
     const int64_t delta = s3s_cs::item_src_off((int64_t)reinterpret_cast<intptr_t>(e.d_src), (int64_t)reinterpret_cast<intptr_t>(base), 0);
-    const bool ok = s3s_cs::plan_entry_records(
-        &w.c, codec, bs, s->st.open_bytes, e.src_len, e.part_ends, e.n_ends, h_marks, h_pf, enc,
-        [&](const s3s_cs::Unit& u) { return unit_items(codec, u); },
-        [&](const s3s_cs::Unit& u, int32_t at) { h_items[at] = Item{0, 0, kItemIv, -1, u.piece}; },  // the hole the encrypt pass fills
-        [&](const s3s_cs::Unit& u, int32_t at, int32_t& slot) {
-          int32_t it = at;
-          if (codec == S3S_CODEC_SNAPPY) {
-            if (u.first) h_items[it++] = Item{0, 0, kItemSnappyHeader, -1, u.piece};
-            snappy_plan_chunk(h_items, it, slot, delta + u.src_off, u.len, u.piece);
-          } else if (codec == S3S_CODEC_LZF) {
-            h_items[it] = Item{delta + u.src_off, u.len, kItemLzfChunk, slot++, u.piece};
-          } else if (u.len > 0) {
-            h_items[it] = Item{delta + u.src_off, u.len, lz4_chunk_kind(u.len) | (level << 8), slot++, u.piece};
-          } else {
-            h_items[it] = Item{0, 0, kItemLz4End | (level << 8), -1, u.piece};
-          }
-        });
-    if (!ok) return fail(ctx, S3S_E_HIP, "the plan of entry %d does not match its count", w.e);
-    if (do_sum) window_segs(codec, bs, e.src_len, e.part_ends, e.n_ends, h_seg + w.c.first_pp, enc);
-    s3s_cs::seed_pieces(w.c, wi, s->carry, fresh(algo), h_seed, h_pw);
+    if (!stage_window(k, h, &w.c, wi, e, delta, enc ? b.slice(w.e) : nullptr))
+      return fail(ctx, S3S_E_HIP, "the plan of entry %d does not match its count", w.e);
+    if (do_sum) k.segs(e, h.seg + w.c.first_pp);
     h_cuts[wi] = w.c;
-    if (enc) s3s_cs::window_ivs(w.c, b.call_ivs, b.iv_at[(size_t)w.e], s->iv, h_ivs);
     TaskTail& t = h_tails[wi];
     t.first_item = w.c.first_item;
     t.n_items = w.c.n_items;
@@ -646,18 +639,7 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
   int64_t* d_sums = reinterpret_cast<int64_t*>(da + A.sums);
   HIP_TRY(ctx, hipMemcpyAsync(da, hs, A.up, hipMemcpyHostToDevice, ctx->stream));  // the call's one upload
   HIP_TRY(ctx, hipMemsetAsync(da + A.up, 0, A.total - A.up, ctx->stream));
-  if (codec == S3S_CODEC_LZ4) {
-    ctx->lz4_variant_used = s0->lz4_variant;
-    launch_lz4_compress(base, d_items, N, dev<uint32_t>(ctx, B_ITEM_CHECK), dev<uint8_t>(ctx, B_SLOTS), (int32_t)slot_stride,
-                        dev<uint32_t>(ctx, B_ITEM_SIZE), dev<uint32_t>(ctx, B_WORK), (s0->lz4_variant == 11 ? 8 : 10) * ctx->cu_count,
-                        s0->lz4_variant, ctx->stream, nullptr, bs >= kLz4U32From);
-  } else if (codec == S3S_CODEC_LZF) {
-    launch_lzf_compress(base, d_items, N, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);
-  } else {
-    launch_snappy_compress(base, d_items, N, dev<uint8_t>(ctx, B_SLOTS), slot_stride, dev<uint32_t>(ctx, B_ITEM_SIZE), s0->snappy_variant,
-                           ctx->stream);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = k.launch(ctx, base, d_items, N))) return rc;
   if (enc) launch_seed_iv_items(d_items, N, dev<uint32_t>(ctx, B_ITEM_SIZE), ctx->stream);  // once, over the items of the whole call
   // (the scan's own index - the unclamped piece offsets - goes to a buffer nobody reads: the cut kernel writes the clamped ones)
   launch_scan_items_batch(d_tails, m, dev<uint32_t>(ctx, B_ITEM_SIZE), dev<int64_t>(ctx, B_ITEM_OFF), d_pf, dev<int64_t>(ctx, B_OFFSETS),
@@ -678,35 +660,14 @@ int cs_batch_run(CsBatch& b, const s3s_cs::Totals& tot) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                                          // ... and its one wait
 
   // every window's words are checked before any stream moves
-  const int32_t* h_status = reinterpret_cast<const int32_t*>(hs + A.status);
-  const int64_t* h_res = reinterpret_cast<const int64_t*>(hs + A.res);
   std::vector<s3s_cs::Cut> cuts((size_t)m);
+  for (int32_t wi = 0; wi < m; wi++)
+    if (!words_ok(h, wi, b.W[(size_t)wi].c, b.E[b.W[(size_t)wi].e], &cuts[(size_t)wi]))
+      return fail(ctx, S3S_E_HIP, "the capacity cut of entry %d returned an impossible result", b.W[(size_t)wi].e);
   for (int32_t wi = 0; wi < m; wi++) {
-    const CsWin& w = b.W[(size_t)wi];
-    const s3s_cstream_feed_entry& e = b.E[w.e];
-    if (!s3s_cs::cut_from_words(h_res + (size_t)s3s_cs::kCutWords * (size_t)wi, h_status[wi], w.c.n_items, e.src_len, e.dst_capacity, e.n_ends,
-                                &cuts[(size_t)wi]))
-      return fail(ctx, S3S_E_HIP, "the capacity cut of entry %d returned an impossible result", w.e);
-  }
-  for (int32_t wi = 0; wi < m; wi++) {
-    const CsWin& w = b.W[(size_t)wi];
-    s3s_cstream_feed_entry& e = b.E[w.e];
-    s3s_cstream* s = e.stream;
-    const s3s_cs::Cut& c = cuts[(size_t)wi];
+    Entry& e = b.E[b.W[(size_t)wi].e];
     memset(&e.result, 0, sizeof e.result);
-    if (c.need_dst > 0) {  // the window's first unit does not fit its dst: nothing is taken, the stream stays usable
-      e.result.need_dst = c.need_dst;
-      e.status = fail(ctx, S3S_E_CAPACITY, "dst_capacity %lld < %lld image bytes of the next unit", (long long)e.dst_capacity, (long long)c.need_dst);
-      continue;
-    }
-    s3s_cs::commit(&s->st, &s->carry, c, e.part_ends, reinterpret_cast<const int64_t*>(hs + A.piece) + w.c.first_pp,
-                   reinterpret_cast<const int64_t*>(hs + A.len) + w.c.first_len,
-                   do_sum ? reinterpret_cast<const int64_t*>(hs + A.sums) + w.c.first_piece : nullptr, e.out_lengths, e.out_checksums);
-    if (enc) s3s_cs::commit_iv(s->iv, s->st, w.c.open_img, c.parts_closed, h_ivs + 16 * (size_t)w.c.first_piece);
-    e.result.consumed = c.consumed;
-    e.result.out_len = c.out_len;
-    e.result.parts_closed = c.parts_closed;
-    e.status = S3S_OK;
+    e.status = take(ctx, h, b.W[(size_t)wi].c, cuts[(size_t)wi], e);
   }
   return S3S_OK;
 }
@@ -722,38 +683,36 @@ int s3s_cstream_feed_batch_device(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32
   ctx->cstream_batch_enc_entries = 0;  // S3S_OPT_CSTREAM_BATCH_ENC_ENTRIES: the same under IO encryption (key 18 then stays 0)
   std::optional<IvScope> iv_scope;  // under IO encryption the call is a compress call: it consumes the IVs of s3s_set_stream_ivs either way
   if (enc_on(ctx)) iv_scope.emplace(ctx);
-  if (n < 0 || (n > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  if (n < 0 || (n > 0 && !E)) return fail_entries(ctx);
   BatchVerdict<s3s_cstream_feed_entry> verdict(E, n);
   if (n == 0) return verdict.finish(S3S_OK);
   CsBatch b = {ctx, E, n, {}, {}};
   bool batched, any_enc;
   int rc;
   if ((rc = cs_batch_check(b, &batched, &any_enc))) return rc;
-  s3s_cs::Totals tot;
-  if (batched && enc_on(ctx) && !any_enc) batched = false;  // only plain streams on a keyed context: each one's S3S_E_UNSUPPORTED
-  if (batched && enc_on(ctx)) {  // ONE array of IVs for the call, sliced in entry order: any other count before anything runs
-    int64_t want = 0;
-    for (int32_t i = 0; i < n; i++) want += s3s_cs::iv_slice_len(E[i].n_ends);
-    if (ctx->iv_cur_n != want)
-      return fail(ctx, S3S_E_INVALID, "the entries of the batch have %lld pieces (n_ends + 1 each), s3s_set_stream_ivs gave %lld IVs",
-                  (long long)want, (long long)ctx->iv_cur_n);
-    b.enc = true;
+  if (enc_on(ctx) && any_enc) {  // ONE array of IVs for the call, sliced in entry order: any other count before anything runs
+    b.iv_at.resize((size_t)n + 1);  // (with the layer off every encrypted stream is stale: the single feed's refusal)
+    const int64_t want = s3s_cs::slice_ivs(n, [&](int32_t i) { return E[i].n_ends; }, b.iv_at.data());
+    if (ctx->iv_cur_n != want) return fail_iv_count(ctx, want);
     b.call_ivs = ctx->iv_cur;
-    b.iv_at.reserve((size_t)n);
   }
-  if (batched && !cs_batch_windows(b, &tot)) {
+  if (enc_on(ctx) && !any_enc) batched = false;  // only plain streams on a keyed context: each one's S3S_E_UNSUPPORTED
+  b.enc = batched && enc_on(ctx);
+  const CsCodec k(E[0].stream, b.enc);
+  s3s_cs::Totals tot;
+  if (batched && !cs_batch_windows(b, k, &tot)) {  // the call does not fit one plan: nothing of the attempt stays
     batched = false;
     b.W.clear();
     b.host.clear();
-    b.iv_at.clear();
     b.enc = false;
+    b.tiles = 0;
   }
   if (!batched) {  // nothing to batch: one by one, in order
-    if ((rc = cs_one_by_one(b, any_enc))) return rc;
+    for (int32_t i = 0; i < n; i++) b.single(i);
     return verdict.finish(b.first_error());
   }
-  if (tot.m > 0 && (rc = cs_batch_run(b, tot))) return rc;
-  for (int32_t i : b.host) b.single(E[i]);  // (no device work: an argument the single feed refuses, a window that launches nothing)
+  if (tot.m > 0 && (rc = cs_batch_run(b, k, tot))) return rc;
+  for (int32_t i : b.host) b.single(i);  // (no device work: an argument the single feed refuses, a window that launches nothing)
   (b.enc ? ctx->cstream_batch_enc_entries : ctx->cstream_batch_entries) = tot.m;
   return verdict.finish(b.first_error());
 }
@@ -763,7 +722,7 @@ int s3s_cstream_feed_batch(s3s_ctx* ctx, s3s_cstream_feed_entry* E, int32_t n) {
   ctx->err[0] = 0;
   ctx->cstream_batch_entries = 0;
   ctx->cstream_batch_enc_entries = 0;
-  if (n < 0 || (n > 0 && !E)) return fail(ctx, S3S_E_INVALID, "null entry array or negative count");
+  if (n < 0 || (n > 0 && !E)) return fail_entries(ctx);
   BatchVerdict<s3s_cstream_feed_entry> verdict(E, n);
   if (n == 0) return verdict.finish(S3S_OK);
   // the windows and the destinations of ALL entries are staged in the context's workspace: the sum of src_len + dst_capacity

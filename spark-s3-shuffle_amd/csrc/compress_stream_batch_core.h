@@ -1,9 +1,11 @@
-// compress_stream_batch_core.h — the arithmetic of the batched feed of the streaming map side (s3s_cstream_feed_batch*,
-// compress_stream.hip): where the windows of several streams lie in ONE plan, what the device is told about each of them, and
-// how a stream's host state moves once the call's one download has come back.  No HIP in here: the file builds for the host
-// alone (tests/model/cstream_batch_model.cpp runs it under the sanitizers against the Python model of the contract,
-// tests/cstream_units.py) and for the device (cstream_cut_batch_kernel and gather_items_cut_batch_kernel,
-// compress_stream_batch_kernels.hip, read CutEntry).  commit() is the single feed's commit step too.
+// compress_stream_batch_core.h — the host rules of BOTH feeds of the streaming map side (s3s_cstream_feed* and
+// s3s_cstream_feed_batch*, compress_stream.hip): what a window counts, which entries are refused, answered on the host or
+// become windows, where the windows of one call lie in ONE plan (the single feed is a call of one window), what the device is
+// told about each of them, and how a stream's host state moves once the download has come back (take_window).  No HIP in here
+// and no allocation: the file builds for the host alone (tests/model/cstream_batch_model.cpp runs these very functions under
+// the sanitizers against the Python model of the contract, tests/cstream_units.py) and for the device (cstream_cut_batch_kernel
+// and gather_items_cut_batch_kernel, compress_stream_batch_kernels.hip, read CutEntry).  What a codec's unit is in items, slots
+// and checksum segments (s3s_ctx.h) comes in through functors.
 //
 // Under IO encryption (tests/model/cstream_batch_encrypted_model.cpp against tests/cstream_units_encrypted.py)
 // the up part of the arena grows by the call's IVs (16 bytes per piece, at first_piece), one PassWindow per batched window and
@@ -53,6 +55,52 @@ constexpr int64_t kBatchMax = 0x7fffff00ll;  // what an int32 index of the call 
 // the arguments the single feed answers S3S_E_INVALID (null_with_length: a null pointer next to a non-zero length, the caller's test)
 inline bool window_refused(int64_t src_len, const int64_t* ends, int32_t n_ends, int64_t dst_capacity, bool null_with_length) {
   return src_len < 0 || n_ends < 0 || dst_capacity < 0 || null_with_length || !ends_valid(src_len, ends, n_ends);
+}
+
+// what a window's units come to: plan items (with the IV records), codec slots, units.  items_of(u) / slots_of(u): of one unit
+struct Count {
+  int64_t items = 0, slots = 0, units = 0;
+};
+template <typename ItemsOf, typename SlotsOf>
+inline Count count_window(int codec, int64_t bs, int64_t open_bytes, int64_t src_len, const int64_t* ends, int32_t n_ends, bool encrypted,
+                          ItemsOf&& items_of, SlotsOf&& slots_of) {
+  Count n;
+  n.units = plan_units(codec, bs, open_bytes, src_len, ends, n_ends, [&](const Unit& u) {
+    n.items += iv_records(u, encrypted) + items_of(u);
+    n.slots += slots_of(u);
+  }).n_units;
+  return n;
+}
+
+// Worst-case checksum segments of a window's pieces: segs_of(source bytes of a piece) = the segments of the most image bytes
+// it can become.  seg_start (or null): n_ends + 2 entries.  -1: more than an int32 index holds ("window too large")
+template <typename SegsOf>
+inline int64_t piece_segs(int64_t src_len, const int64_t* ends, int32_t n_ends, int32_t* seg_start, SegsOf&& segs_of) {
+  int64_t segs = 0;
+  for (int32_t j = 0; j <= n_ends; j++) {
+    const int64_t a = j == 0 ? 0 : ends[j - 1], b = j < n_ends ? ends[j] : src_len;
+    if (seg_start) seg_start[j] = (int32_t)segs;
+    segs += segs_of(b - a);
+    if (segs > kBatchMax) return -1;
+  }
+  if (seg_start) seg_start[n_ends + 1] = (int32_t)segs;
+  return segs;
+}
+
+// An entry of a batched call: refused by its arguments (window_refused), answered on the host - its window launches nothing,
+// or has more items or segments (segs < 0) than one feed takes: the single feed's answer either way - or a window of the batch
+enum Route { kRouteRefused, kRouteHost, kRouteWindow };
+inline Route route_entry(bool refused, const Count& n, int64_t segs) {
+  if (refused) return kRouteRefused;
+  return n.items == 0 || n.items > kBatchMax || segs < 0 ? kRouteHost : kRouteWindow;
+}
+
+// the cut of a window that launches nothing: every end is passed; without one the caller learns the window that holds a unit
+inline Cut cut_nothing(int32_t n_ends, int64_t need_src_unit) {
+  Cut c;
+  c.parts_closed = n_ends;
+  if (n_ends == 0) c.need_src = need_src_unit;
+  return c;
 }
 
 // a plan item's source: the unit's offset in its window, seen from the call's base pointer (addresses as integers)
@@ -137,8 +185,8 @@ struct Arena {
   }
 };
 
-// The plan records of one entry, written into the call's arrays: the single feed's loop (compress_stream.hip) with the entry's
-// places added.  items_of(u) = the plan items of unit u; emit(u, at, slot) writes them at item `at` of the CALL (slot: the
+// The plan records of one entry, written into the call's arrays: the ONE plan loop of both feeds (the single feed's window is
+// an entry whose places are all 0).  items_of(u) = the plan items of unit u; emit(u, at, slot) writes them at item `at` of the CALL (slot: the
 // call's slot counter, advanced) with src_off = src_delta + the unit's offset.  marks / part_first: the call's arrays.
 // false: the plan does not match the counts the entry was reserved with (nothing may be launched).
 // Under IO encryption one more record (emit_iv(u, at): kItemIv) goes in front of the items of every unit that starts its
@@ -187,10 +235,11 @@ inline bool plan_entry_encrypted(CutEntry* c, int codec, int64_t bs, int64_t ope
 }
 
 // the seeds of an entry's pieces: the stream's carried state continues into the first, a fresh state starts the others
+// (piece_entry: the call's piece -> entry map, or null)
 inline void seed_pieces(const CutEntry& c, int32_t entry, int64_t carry, int64_t fresh, int64_t* seeds, int32_t* piece_entry) {
   for (int32_t j = 0; j < c.n_pieces; j++) {
     seeds[c.first_piece + j] = j == 0 ? carry : fresh;
-    piece_entry[c.first_piece + j] = entry;
+    if (piece_entry) piece_entry[c.first_piece + j] = entry;
   }
 }
 
@@ -207,6 +256,13 @@ struct IvSlicer {
     return mine;
   }
 };
+// "the entries of the batch have N pieces": entry i's slice is [at[i], at[i + 1]) of the call's IVs, N = at[n] is returned
+template <typename NEndsOf>
+inline int64_t slice_ivs(int32_t n, NEndsOf&& n_ends_of, int64_t* at) {
+  IvSlicer slices;
+  for (int32_t i = 0; i < n; i++) at[i] = slices.take(n_ends_of(i));
+  return at[n] = slices.at;
+}
 
 // the IVs of one batched window, into the call's array at its pieces: the entry's slice, entry 0 replaced by the IV the stream
 // carries while its open partition already has image bytes
@@ -304,6 +360,35 @@ inline void commit(State* st, int64_t* carry, const Cut& c, const int64_t* ends,
     *carry = sums[c.parts_closed];
   }
   advance(st, c, ends, piece_off);
+}
+
+// ---- the two ends of a feed, for the single feed and for every window of a batch ------------------------------------------------
+// iv: the stream's carried IV (null: not under IO encryption); r: an s3s_cstream_result, zeroed.
+// Answered on the host, nothing written (cut_nothing, or S3S_CODEC_NONE's cut with out_len 0):
+template <typename Result>
+inline void answer_on_host(State* st, int64_t* carry, uint8_t* iv, int64_t fresh, const Cut& c, int64_t* out_lengths, int64_t* out_checksums,
+                           Result* r) {
+  commit_nothing(st, carry, fresh, c.parts_closed, out_lengths, out_checksums);
+  if (iv) commit_nothing_iv(iv, c.parts_closed);
+  r->need_src = c.need_src;
+  r->parts_closed = c.parts_closed;
+}
+// Behind the download, a cut that passed cut_from_words (or S3S_CODEC_NONE's).  false: S3S_E_CAPACITY - the first unit does not
+// fit dst, r->need_dst says what does, nothing is taken and the stream stays usable.  feed_ivs: the IVs the feed ran with
+template <typename Result>
+inline bool take_window(State* st, int64_t* carry, uint8_t* iv, const Cut& c, const int64_t* ends, const int64_t* piece_off, const int64_t* lengths,
+                        const int64_t* sums, const uint8_t* feed_ivs, int64_t* out_lengths, int64_t* out_checksums, Result* r) {
+  if (c.need_dst > 0) {
+    r->need_dst = c.need_dst;
+    return false;
+  }
+  const State before = *st;
+  commit(st, carry, c, ends, piece_off, lengths, sums, out_lengths, out_checksums);
+  if (iv) commit_iv(iv, *st, before.open_img, c.parts_closed, feed_ivs);
+  r->consumed = c.consumed;
+  r->out_len = c.out_len;
+  r->parts_closed = c.parts_closed;
+  return true;
 }
 
 }  // namespace s3s_cs

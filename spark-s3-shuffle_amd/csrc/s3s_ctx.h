@@ -253,6 +253,16 @@ inline void snappy_plan_chunk(ItemT* items, int32_t& it, int32_t& slot, int64_t 
     items[it++] = ItemT{src_off + f, fl, kItemSnappyFrag, slot++, part};
   }
 }
+// What ONE codec block [src_off, src_off + len) of partition `part` is in the plan of every compress call - the one-shot call,
+// the task batch and the streaming feeds.  level: lz4_level(bs); last: the last block of its stream (Zstandard's kind bit)
+template <typename ItemT>
+inline void plan_codec_block(ItemT* items, int32_t& it, int32_t& slot, int codec, int level, int64_t src_off, int32_t len, int32_t part,
+                             bool last) {
+  if (codec == S3S_CODEC_SNAPPY) snappy_plan_chunk(items, it, slot, src_off, len, part);
+  else if (codec == S3S_CODEC_ZSTD) items[it++] = ItemT{src_off, len, kItemZstdBlock | (last << 8), slot++, part};
+  else if (codec == S3S_CODEC_LZF) items[it++] = ItemT{src_off, len, kItemLzfChunk, slot++, part};
+  else items[it++] = ItemT{src_off, len, lz4_chunk_kind(len) | (level << 8), slot++, part};
+}
 // bytes between the slots of one Snappy call: a slot holds at most one fragment's output
 inline int64_t snappy_slot_stride(int64_t bs) {
   const int64_t n = bs < kSnappyFragment ? bs : kSnappyFragment;
@@ -263,6 +273,10 @@ inline int64_t snappy_slot_stride(int64_t bs) {
 // an LZF block is written in full before the chunk is declared stored
 inline int64_t codec_slot_stride(int codec, int64_t bs) {
   return (int64_t)kSlotHeader + (codec == S3S_CODEC_LZF ? (int64_t)kLzfSlotPayload : ((bs + 15) & ~int64_t(15)));
+}
+// ... of a compress call of any codec
+inline int64_t compress_slot_stride(int codec, int64_t bs) {
+  return codec == S3S_CODEC_SNAPPY ? snappy_slot_stride(bs) : codec_slot_stride(codec, bs);
 }
 
 inline int64_t effective_block(const s3s_ctx* ctx, int codec) {

@@ -241,6 +241,11 @@ def _rounds(prog, streams, rng, codec, bs, algo, seed, big, max_rounds):
             elif kind == 2 and ends:
                 ends = ends[:-1] + [wlen + 1]  # beyond the window
                 bad.append(i)
+            elif kind == 3:
+                ends = None  # n_ends = -1: refused, and under IO encryption still one IV of the call's
+                bad.append(i)
+            elif kind == 4 and ends and ends[-1] == wlen:
+                ends = ends[:-1]  # an end at the window's very end held back: a later window passes it, maybe one that launches nothing
             entries.append((i, 1 << 20 | int(slots[i]) << 24, wlen, cap, ends))
         got, windows = prog.round(entries, streams)
         batched += windows

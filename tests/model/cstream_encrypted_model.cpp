@@ -2,8 +2,9 @@
 // INFRASTRUCTURE.  tests/test_compress_stream_encrypted_cpu.py builds it with -fsanitize=address,undefined; every array has
 // exactly the size in use, so that an index one too far is a sanitizer report.
 //
-//   plan   the arithmetic of spark-s3-shuffle_amd/csrc/compress_stream_core.h: a window's plan with IV records (iv_records,
-//          mark_unit, mark_ends_after), the cut over the marks as cstream_cut_kernel makes it (cut_lane), the encrypted NONE cut
+//   plan   the arithmetic of spark-s3-shuffle_amd/csrc/compress_stream_core.h and, as the single feed calls it for a batch of one,
+//          compress_stream_batch_core.h: a window's count and its plan with IV records (count_window, plan_entry_encrypted), the
+//          empty window and the take step, the cut over the marks as cstream_cut_kernel makes it (cut_lane), the encrypted NONE cut
 //          (none_cut_encrypted), feed_bound_encrypted and the stream's state, driven by a schedule of feeds and the PLAIN image
 //          sizes of a map output's units; compared field for field with the Python model (tests/cstream_units_encrypted.py).
 //            stdin:   codec bs nparts / nparts lines: n_units size... / feeds, one a line: src_len cap n_ends end...
@@ -20,9 +21,14 @@
 #include <vector>
 
 #include "../../spark-s3-shuffle_amd/csrc/aes_ctr_stream_core.h"
-#include "../../spark-s3-shuffle_amd/csrc/compress_stream_core.h"
+#include "../../spark-s3-shuffle_amd/csrc/compress_stream_batch_core.h"
 
 namespace {
+
+struct Result {  // s3s_cstream_result
+  int64_t consumed = 0, out_len = 0, need_src = 0, need_dst = 0;
+  int32_t parts_closed = 0;
+};
 
 int run_plan() {
   int codec = 0, nparts = 0;
@@ -42,7 +48,8 @@ int run_plan() {
     }
   }
   s3s_cs::State st;
-  int64_t n_closed = 0;
+  int64_t n_closed = 0, carry = 0;
+  uint8_t iv[16] = {};
   long long src_len, cap;
   int n_ends;
   while (scanf("%lld %lld %d", &src_len, &cap, &n_ends) == 3) {
@@ -67,47 +74,39 @@ int run_plan() {
       if (counted.consumed != c.consumed || counted.out_len != c.out_len || counted.need_dst != c.need_dst || counted.parts_closed != c.parts_closed)
         return 4;
     } else {
-      // count, then build: the records of every unit (an IV record in front of a partition's first block, a Snappy header, the
-      // block itself), their image sizes, their marks and the first record of every piece, as s3s_cstream_feed_device does
-      int64_t n_items = 0;
-      s3s_cs::plan_units(codec, bs, st.open_bytes, src_len, ends.get(), n_ends, [&](const s3s_cs::Unit& u) {
-        n_items += s3s_cs::iv_records(u, true) + (codec == s3s_cs::kCodecSnappy && u.first) + 1;
-      });
+      // count, then build - the single feed's batch of one: the records of every unit (an IV record in front of a partition's
+      // first block, a Snappy header, the block itself), their marks and the first record of every piece; here with their image sizes
+      const auto items_of = [&](const s3s_cs::Unit& u) { return (codec == s3s_cs::kCodecSnappy && u.first) + 1; };
+      const s3s_cs::Count cnt = s3s_cs::count_window(codec, bs, st.open_bytes, src_len, ends.get(), n_ends, true, items_of,
+                                                     [](const s3s_cs::Unit& u) { return u.len > 0; });
+      const int64_t n_items = cnt.items;
+      s3s_cs::Totals tot;
+      s3s_cs::CutEntry plan = s3s_cs::reserve(&tot, cnt.items, cnt.slots, n_ends, 0, cap, st.open_img);
       std::unique_ptr<s3s_cs::Mark[]> marks(new s3s_cs::Mark[(size_t)n_items]);
-      std::unique_ptr<int64_t[]> item_off(new int64_t[(size_t)n_items + 1]);
+      std::unique_ptr<int64_t[]> size(new int64_t[(size_t)n_items]), item_off(new int64_t[(size_t)n_items + 1]);
       std::unique_ptr<int32_t[]> part_first(new int32_t[(size_t)n_pieces + 1]);
-      int32_t it = 0, piece = 0, prev0 = 0, first_last = -1, ends0 = 0;
+      const bool planned = s3s_cs::plan_entry_encrypted(
+          &plan, codec, bs, st.open_bytes, src_len, ends.get(), n_ends, marks.get(), part_first.get(), items_of,
+          [&](const s3s_cs::Unit&, int32_t at) { size[(size_t)at] = 16; },
+          [&](const s3s_cs::Unit& u, int32_t at, int32_t& slot) {
+            const int64_t part = n_closed + u.piece;
+            const int64_t piece_start = u.piece == 0 ? 0 : ends[(size_t)u.piece - 1];
+            const int64_t had = u.piece == 0 ? st.open_bytes : 0;
+            const int64_t idx = u.len > 0 ? (had + u.src_off - piece_start) / bs : n_sizes[(size_t)part] - 1;
+            int64_t body = sizes[(size_t)part][(size_t)idx];
+            if (codec == s3s_cs::kCodecSnappy && u.first) {
+              size[(size_t)at++] = 16;
+              body -= 16;
+            }
+            size[(size_t)at] = body;
+            slot += u.len > 0;
+          });
+      if (!planned) return 4;
       item_off[0] = 0;
-      part_first[0] = 0;
-      s3s_cs::plan_units(codec, bs, st.open_bytes, src_len, ends.get(), n_ends, [&](const s3s_cs::Unit& u) {
-        s3s_cs::mark_ends_after(marks.get(), prev0, it, u.ends_before);
-        if (it == 0) ends0 = u.ends_before;
-        while (piece < u.piece) part_first[(size_t)++piece] = it;
-        prev0 = it;
-        const int64_t part = n_closed + u.piece;
-        const int64_t piece_start = u.piece == 0 ? 0 : ends[(size_t)u.piece - 1];
-        const int64_t had = u.piece == 0 ? st.open_bytes : 0;
-        const int64_t idx = u.len > 0 ? (had + u.src_off - piece_start) / bs : n_sizes[(size_t)part] - 1;
-        int64_t body = sizes[(size_t)part][(size_t)idx];
-        if (s3s_cs::iv_records(u, true)) {
-          item_off[(size_t)it + 1] = item_off[(size_t)it] + 16;
-          it++;
-        }
-        if (codec == s3s_cs::kCodecSnappy && u.first) {
-          item_off[(size_t)it + 1] = item_off[(size_t)it] + 16;
-          body -= 16;
-          it++;
-        }
-        item_off[(size_t)it + 1] = item_off[(size_t)it] + body;
-        it++;
-        s3s_cs::mark_unit(marks.get(), prev0, it, u, n_ends);
-        if (first_last < 0) first_last = it - 1;
-      });
-      while (piece < n_pieces) part_first[(size_t)++piece] = it;
-      if (it != n_items) return 4;
+      for (int64_t i = 0; i < n_items; i++) item_off[(size_t)i + 1] = item_off[(size_t)i] + size[(size_t)i];
+      const int32_t first_last = plan.first_last, ends0 = plan.ends0;
       if (n_items == 0) {
-        c.parts_closed = n_ends;
-        if (n_ends == 0) c.need_src = codec == s3s_cs::kCodecLzf ? s3s_cs::kLzfBlock : bs;
+        c = s3s_cs::cut_nothing(n_ends, codec == s3s_cs::kCodecLzf ? s3s_cs::kLzfBlock : bs);
         for (int j = 0; j <= n_pieces; j++) piece_off[(size_t)j] = 0;
       } else {  // cstream_cut_kernel, serially
         int32_t best = -1;
@@ -124,16 +123,16 @@ int run_plan() {
         }
       }
     }
-    if (c.need_dst) {
-      printf("-2 0 0 0 %lld 0 %lld\n", (long long)c.need_dst, bound);
+    std::unique_ptr<int64_t[]> lengths(new int64_t[(size_t)c.parts_closed]);
+    std::unique_ptr<uint8_t[]> feed_ivs(new uint8_t[16 * (size_t)n_pieces]());
+    Result r;
+    if (!s3s_cs::take_window(&st, &carry, iv, c, ends.get(), piece_off.get(), nullptr, nullptr, feed_ivs.get(), lengths.get(), nullptr, &r)) {
+      printf("-2 0 0 0 %lld 0 %lld\n", (long long)r.need_dst, bound);
       continue;
     }
-    std::unique_ptr<int64_t[]> lengths(new int64_t[(size_t)c.parts_closed]);
-    s3s_cs::closed_lengths(st, c, piece_off.get(), lengths.get());
-    s3s_cs::advance(&st, c, ends.get(), piece_off.get());
-    n_closed += c.parts_closed;
-    printf("0 %lld %lld %lld 0 %d %lld", (long long)c.consumed, (long long)c.out_len, (long long)c.need_src, (int)c.parts_closed, bound);
-    for (int j = 0; j < c.parts_closed; j++) printf(" %lld", (long long)lengths[(size_t)j]);
+    n_closed += r.parts_closed;
+    printf("0 %lld %lld %lld 0 %d %lld", (long long)r.consumed, (long long)r.out_len, (long long)c.need_src, (int)r.parts_closed, bound);
+    for (int j = 0; j < r.parts_closed; j++) printf(" %lld", (long long)lengths[(size_t)j]);
     printf("\n");
   }
   return 0;

@@ -1,6 +1,6 @@
 // cstream_model.cpp — the host arithmetic of the streaming map side (spark-s3-shuffle_amd/csrc/compress_stream_core.h) as a
-// stand-alone program: the plan of a window's units, the cut at a capacity and the stream's state, driven by a schedule of
-// feeds and the image sizes of a map output's units.  tests/test_compress_stream_cpu.py builds it with
+// stand-alone program: the plan of a window's units, the cut at a capacity and the stream's state (the take step of
+// compress_stream_batch_core.h, as the feeds call it), driven by a schedule of feeds and the image sizes of a map output's units.  tests/test_compress_stream_cpu.py builds it with
 // -fsanitize=address,undefined and compares every feed, field for field, with the Python model (tests/cstream_units.py).
 // Every array has exactly the size in use, so that an index one too far is a sanitizer report.
 //
@@ -12,7 +12,12 @@
 #include <memory>
 #include <vector>
 
-#include "../../spark-s3-shuffle_amd/csrc/compress_stream_core.h"
+#include "../../spark-s3-shuffle_amd/csrc/compress_stream_batch_core.h"
+
+struct Result {  // s3s_cstream_result
+  int64_t consumed = 0, out_len = 0, need_src = 0, need_dst = 0;
+  int32_t parts_closed = 0;
+};
 
 int main() {
   int codec = 0, nparts = 0;
@@ -32,7 +37,7 @@ int main() {
     }
   }
   s3s_cs::State st;
-  int64_t n_closed = 0;
+  int64_t n_closed = 0, carry = 0;
   long long src_len, cap;
   int n_ends;
   while (scanf("%lld %lld %d", &src_len, &cap, &n_ends) == 3) {
@@ -80,16 +85,15 @@ int main() {
         piece_off[(size_t)j] = o < c.out_len ? o : c.out_len;
       }
     }
-    if (c.need_dst) {
-      printf("-2 0 0 0 %lld 0\n", (long long)c.need_dst);
+    std::unique_ptr<int64_t[]> lengths(new int64_t[(size_t)c.parts_closed]);
+    Result r;
+    if (!s3s_cs::take_window(&st, &carry, nullptr, c, ends.get(), piece_off.get(), nullptr, nullptr, nullptr, lengths.get(), nullptr, &r)) {
+      printf("-2 0 0 0 %lld 0\n", (long long)r.need_dst);
       continue;
     }
-    std::unique_ptr<int64_t[]> lengths(new int64_t[(size_t)c.parts_closed]);
-    s3s_cs::closed_lengths(st, c, piece_off.get(), lengths.get());
-    s3s_cs::advance(&st, c, ends.get(), piece_off.get());
-    n_closed += c.parts_closed;
-    printf("0 %lld %lld %lld 0 %d", (long long)c.consumed, (long long)c.out_len, (long long)c.need_src, (int)c.parts_closed);
-    for (int j = 0; j < c.parts_closed; j++) printf(" %lld", (long long)lengths[(size_t)j]);
+    n_closed += r.parts_closed;
+    printf("0 %lld %lld %lld 0 %d", (long long)r.consumed, (long long)r.out_len, (long long)c.need_src, (int)r.parts_closed);
+    for (int j = 0; j < r.parts_closed; j++) printf(" %lld", (long long)lengths[(size_t)j]);
     printf("\n");
   }
   return 0;

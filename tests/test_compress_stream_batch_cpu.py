@@ -123,6 +123,12 @@ MUTANTS = [
     ("len = arena_al(piece + 8 * PP);", "len = arena_al(piece + 8 * P);"),                                       # n + 1 offsets an entry
     ("piece_entry[c.first_piece + j] = entry;", "piece_entry[c.first_piece + j] = entry + 1;"),
     ("if (it == 0) c->ends0 = u.ends_before;", "if (it == 0) c->ends0 = 0;"),
+    # the rules both feeds share: the window that launches nothing, the take step, the first piece's seed
+    ("if (n_ends == 0) c.need_src = need_src_unit;", "if (n_ends != 0) c.need_src = need_src_unit;"),
+    ("c.parts_closed = n_ends;", "c.parts_closed = 0;"),
+    ("if (c.need_dst > 0) {", "if (c.need_dst < 0) {"),                                                           # need_dst, and the stream moves all the same
+    ("seeds[c.first_piece + j] = j == 0 ? carry : fresh;", "seeds[c.first_piece + j] = j < 0 ? carry : fresh;"),   # fresh for the first piece too
+    ("return n.items == 0 || n.items > kBatchMax", "return n.items != 0 || n.items > kBatchMax"),                   # which entries are windows
 ]
 
 

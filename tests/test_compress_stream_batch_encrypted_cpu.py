@@ -292,6 +292,11 @@ def _rounds(prog, streams, rng, codec, bs, algo, seed, max_rounds):
             elif kind == 2 and ends:
                 ends = ends[:-1] + [wlen + 1]  # beyond the window
                 bad.append(i)
+            elif kind == 3:
+                ends = None  # n_ends = -1: refused, and under IO encryption still one IV of the call's
+                bad.append(i)
+            elif kind == 4 and ends and ends[-1] == wlen:
+                ends = ends[:-1]  # an end at the window's very end held back: a later window passes it, maybe one that launches nothing
             entries.append((i, 1 << 20 | int(slots[i]) << 24, wlen, cap, ends))
         other_iv0 = bool(tally["rounds"] % 2)
         if tally["rounds"] % 7 == 3:  # a wrong IV count: refused before anything runs, with every stream unchanged
@@ -301,6 +306,7 @@ def _rounds(prog, streams, rng, codec, bs, algo, seed, max_rounds):
             for (i, *_), g in zip(entries, got):
                 assert g["code"] == NOT_RUN and (g["pos"], g["written"], g["open_bytes"], g["open_img"], g["carry"], g["iv"]) == _state(streams[i], algo, g)
         got, windows = prog.round(entries, streams, other_iv0)
+        assert windows != "V", "the program refused the right IV count"
         tally["batched"] += windows
         tally["hosted"] += len(entries) - len(bad) - windows - sum(streams[i].stale and i not in bad for i, *_ in entries)
         for (i, _, wlen, cap, ends), g in zip(entries, got):
@@ -360,12 +366,18 @@ MUTANTS = [
     ("p.ivs = ivs + kIvBytes * (size_t)cuts[w].first_piece;", "p.ivs = ivs + kIvBytes * (size_t)cuts[w].first_pp;"),  # the IVs of an n + 1 array
     ("} else if (parts_closed > 0 || front == 0) {", "} else if (parts_closed > 0 && front == 0) {"),             # the next open partition's IV kept
     ("if (lead) emit_iv(u, c->first_item + it);", "if (lead) emit_iv(u, it);"),                                   # the IV record of the call, not of the entry
+    # the rules both feeds share: the take step's IV bookkeeping, the slice of a refused entry, the empty window's IV
+    ("if (iv) commit_iv(iv, *st, before.open_img,", "if (iv) commit_iv(iv, before, before.open_img,"),            # the state from before the commit
+    ("return (int64_t)(n_ends > 0 ? n_ends : 0) + 1;", "return (int64_t)(n_ends > -2 ? n_ends : 0) + 1;"),        # an entry with n_ends < 0 has one IV too
+    ("if (iv) commit_nothing_iv(iv, c.parts_closed);", "if (iv) commit_nothing_iv(iv, 0);"),
 ]
 
 
 def _mutant_rounds(oracle, exe, tmp_path, old):
     if "kPassTile - 1) / kPassTile" in old:
         _tile_lead_round(oracle, exe, tmp_path)
+    if "commit_nothing_iv" in old:
+        _held_back_end_round(oracle, exe, tmp_path)
     for run in range(4):
         run_rounds(oracle, exe, tmp_path, cu.LZ4, 64, cb.ADLER, seed=1000 * cu.LZ4 + run, n_streams=[2, 9, 5, 3][run])
 
@@ -430,8 +442,36 @@ def _tile_lead_round(oracle, exe, tmp_path):
         raise
 
 
+def _held_back_end_round(oracle, exe, tmp_path):
+    """two Snappy streams whose first partition is one whole block: round one takes the block and holds the end back, round
+    two is an empty window with that end - it launches nothing, closes a partition that has image bytes and wipes its IV -
+    round three takes the rest.  (An LZ4 partition with bytes closes with its end frame: a window with a unit.)"""
+    rng = np.random.default_rng(5)
+    streams = [KeyedCase(oracle, cu.SNAPPY, 1024, rng.integers(0, 256, 1024 + r, dtype=np.uint8), np.array([0, 1024, 1024 + r], np.int64),
+                         rng.integers(1, 256, (2, 16), dtype=np.uint8)) for r in (5, 1024)]
+    prog = KeyedProgram(exe, tmp_path, cu.SNAPPY, 1024, cb.CRC, streams)
+    try:
+        for wlen, ends, windows in ((1024, [], 2), (0, [0], 0), (1 << 20, None, 2)):
+            entries = []
+            for i, s in enumerate(streams):
+                w = min(wlen, s.offs[-1] - s.model.pos)
+                entries.append((i, 1 << 20 | i << 24, w, 1 << 30, cu.ends_in_window(s.offs, s.model.pos, s.model.n_closed, w) if ends is None else ends))
+            got, m = prog.round(entries, streams)
+            assert m == windows
+            for (i, _, w, cap, e), g in zip(entries, got):
+                want = streams[i].model.feed(w, e, cap)
+                assert (g["code"], g["consumed"], g["out_len"], g["need_src"], g["need_dst"], g["parts_closed"], tuple(g["lengths"])) == want.fields()
+                assert (g["pos"], g["written"], g["open_bytes"], g["open_img"], g["carry"], g["iv"]) == _state(streams[i], cb.CRC, g)
+        prog.close()
+    except BaseException:
+        prog.kill()
+        raise
+    assert all(s.done for s in streams)
+
+
 def test_the_unmutated_header_passes_the_mutants_rounds(oracle, model_exe, tmp_path):
     _tile_lead_round(oracle, model_exe, tmp_path)
+    _held_back_end_round(oracle, model_exe, tmp_path)
 
 
 @pytest.mark.parametrize("old,new", MUTANTS, ids=[str(i) for i in range(len(MUTANTS))])

@@ -290,6 +290,44 @@ def test_a_wrong_iv_count_is_refused_and_the_array_consumed(ctxs, dev):
     assert rig.enc_calls >= 2
 
 
+def test_only_plain_streams_on_a_keyed_context_go_one_by_one(ctxs, dev):
+    """kept as found: a batch without a single keyed stream on a keyed context is not batched and wants no IVs - every entry
+    gets the single feed's S3S_E_UNSUPPORTED as its own status, nothing is launched, keys 18 and 19 stay 0"""
+    ctx = ctxs(LZ4, 1)[0]
+    ctx.set_option(1, 64)
+    plain = [ctx.compress_stream(LZ4, ADLER) for _ in range(3)]  # opened before the layer is on
+    ctx.set_io_encryption(KEY)
+    d_src, d_dst = dev.alloc(4096), dev.alloc(3 * 4096)
+    res = ctx.compress_stream_feed_batch([(s, d_src, 100, [100], d_dst + 4096 * i, 4096) for i, s in enumerate(plain)])
+    assert ctx.last_compress_batch_code == E_UNSUPPORTED and [r.code for r in res] == [E_UNSUPPORTED] * 3
+    assert ctx.get_option(OPT_BATCH_ENC) == 0 and ctx.get_option(OPT_BATCH) == 0
+    assert all((s.position, s.written) == (0, 0) for s in plain)
+    for s in plain:
+        s.close()
+
+
+def test_a_window_of_too_many_blocks_is_refused_behind_the_checks(ctxs, dev):
+    """kept as found: the single feed counts the blocks of its window (0x7fffff00 of them at most) only behind the argument
+    checks and the IV count check.  A window that claims 2^31 blocks of 64 bytes and has a negative capacity, descending ends or
+    a wrong IV count gets that check's S3S_E_INVALID at once: its blocks are never walked, nothing is launched"""
+    import s3shuffle
+
+    ctx = ctxs(LZ4, 1)[0]
+    ctx.set_option(1, 64)
+    ctx.set_io_encryption(KEY)
+    s = ctx.compress_stream(LZ4, ADLER, encrypted=True)
+    d_src, d_dst = dev.alloc(4096), dev.alloc(4096)
+    huge = 64 << 31
+    for ends, cap, n_ivs in (([], -1, 1), ([huge, 5], 4096, 3), ([], 4096, 2), ([], 4096, None)):
+        if n_ivs is not None:
+            ctx.set_stream_ivs(np.zeros(16 * n_ivs, np.uint8))
+        with pytest.raises(s3shuffle.CodecError) as e:
+            s.feed_device(d_src, huge, ends, d_dst, cap)
+        assert e.value.code == E_INVALID, e.value
+        assert (s.position, s.written) == (0, 0)
+    s.close()
+
+
 # ---- 8. host buffers, many streams ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("codec", [LZ4, SNAPPY, LZF], ids=["lz4", "snappy", "lzf"])
 def test_host_buffers(ctxs, dev, codec):
